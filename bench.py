@@ -18,6 +18,11 @@ BEFORE anything touches the GPU and relays rank 0's line; under an external laun
 of the ranks.  c2 / c3 with N > 1: every rank fits its own material (different seed) -- fits are independent, so there
 is no data-path collective; the fitted parameters + info[] of all steps are gathered to rank 0 with ONE RCCL gather
 at the end of the timed region ("weak" scaling).  c4 / c5: fixed total work ("strong").
+
+A plain run sets up, warms up, times `--steps` steps of the workload's headline and prints the line.  `--full` adds everything
+else the line used to carry: the CPU baselines and the parity against CPU levmar, the dlevmar_bc_dif figures next to the c2 / c3
+headline and, for c2 on one GPU, the configs[2..4] and three-channel sub-lines.  `--dump-outputs DIR` writes what the
+headline's last timed step returned (fitted parameters, info[], return codes) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -213,6 +218,23 @@ def batched_kernel_name(model, method, n):
     return f"resident_fit_kernel<{model}, {m}, true, true>"
 
 
+def dump_outputs(out_dir, arrays, budget=60_000_000):
+    """--dump-outputs: the arrays a caller of the timed path received in its last step, as out_dir/<name>.npy in float64.
+    Arrays with a row per fit that would exceed `budget` bytes in all are cut to a fixed, seeded sample of rows (the same rows
+    in every run), whose indices go to rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        n = next(iter(arrays.values())).shape[0]
+        keep = int(n * budget / (total + 8 * n))
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -302,8 +324,9 @@ def batched_cpu_subset(workload, entry, count=64):
     return {"p": ps, "info": infos, "ret": rets, "kind": kind}
 
 
-def batched_line(args, workload, entry, ctx, steps, warmup, cpu_base=None, cpu_subset=None):
-    """one multi-surfel workload (c4 / c5) on the ranks of `ctx`; returns rank 0's line (None elsewhere)"""
+def batched_line(args, workload, entry, ctx, steps, warmup, cpu_base=None, cpu_subset=None, dump=None):
+    """one multi-surfel workload (c4 / c5) on the ranks of `ctx`; returns rank 0's line (None elsewhere).  dump: directory for
+    the gathered rows of the last timed step (--dump-outputs)"""
     from brdf_amd import synth
     torch, dist, rank, world, backend, dev, stub = ctx
     S, n = {"c4": (65536, 4096), "c5": (1 << 20, 256)}[workload]
@@ -397,6 +420,9 @@ def batched_line(args, workload, entry, ctx, steps, warmup, cpu_base=None, cpu_s
             line["event_ms_per_step"] = ev[0].elapsed_time(ev[1]) / steps
         # the gathered rows (p, info, ret of every surfel, in surfel order) as one digest: runs on 1, 2, 4, 8 ranks must agree bit for bit
         line["result_sha256"] = hashlib.sha256(out.cpu().contiguous().numpy().tobytes()).hexdigest()[:16]
+        if dump:
+            rows = out.cpu().numpy()
+            dump_outputs(dump, {"p": rows[:, :3], "info": rows[:, 3:13], "ret": rows[:, 13]})
         if stub:
             line["stub_checksum"] = float(out[:, :3].sum().item())
         if cpu_base is not None:
@@ -425,14 +451,14 @@ def main_batched(args):
     method = 0 if args.entry == "dif" else 1
     S, n = {"c4": (65536, 4096), "c5": (1 << 20, 256)}[args.workload]
     cpu_subset = None
-    if (not args.no_cpu and int(os.environ.get("WORLD_SIZE", "1")) == 1 and os.environ.get("BRDF_BENCH_STUB") != "1"):
+    if (args.full and not args.no_cpu and int(os.environ.get("WORLD_SIZE", "1")) == 1 and os.environ.get("BRDF_BENCH_STUB") != "1"):
         # before this process touches the GPU: the workers are plain child processes (numpy + ctypes, no torch, no HIP)
         cpu_base = cpu_baseline_batched(method, 2, args.samples or n, args.surfels or S)
         if not args.surfels and not args.samples:
             cpu_subset = batched_cpu_subset(args.workload, args.entry)
     ctx = dist_setup(args)
     torch, dist, rank, world = ctx[0], ctx[1], ctx[2], ctx[3]
-    line = batched_line(args, args.workload, args.entry, ctx, args.steps, args.warmup, cpu_base, cpu_subset)
+    line = batched_line(args, args.workload, args.entry, ctx, args.steps, args.warmup, cpu_base, cpu_subset, args.dump_outputs)
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1 or FORCE_COLL:
@@ -452,9 +478,10 @@ def single_cpu_refs(model, angles, x, timed=True):
             "bc_dif": cpu_baseline(1, model, angles, x, p0, opts, lb, ub, itmax, budget_s=6.0 if timed else 0.0)}
 
 
-def single_line(args, model, ctx, steps, warmup, angles, x, rank0_cpu):
-    """one single-material workload (c2 / c3): every rank fits its own material `steps` times through both entry points;
-    returns (rank 0's line or None, exit code)"""
+def single_line(args, model, ctx, steps, warmup, angles, x, rank0_cpu, dump=None):
+    """one single-material workload (c2 / c3): every rank fits its own material `steps` times through dlevmar_dif (and, with
+    --full, through dlevmar_bc_dif); returns (rank 0's line or None, exit code).  dump: directory for what rank 0's last timed
+    dlevmar_dif fit returned (--dump-outputs)"""
     from brdf_amd import synth
     torch, dist, rank, world, backend, dev, stub = ctx
     p0, opts, lb, ub, itmax = synth.P0[model], synth.OPTS, synth.LB, synth.UB, synth.ITMAX
@@ -511,6 +538,8 @@ def single_line(args, model, ctx, steps, warmup, angles, x, rank0_cpu):
             dist.barrier()
         torch.cuda.synchronize()
         wall = time.perf_counter() - t0
+        if dump and method == 0 and rank == 0:
+            dump_outputs(dump, {"p": r.p, "info": r.info, "ret": [r.ret]})
         ev_ms = ev0.elapsed_time(ev1)
         fit_ms = sum(a.elapsed_time(b) for a, b in evs) if evs else ev_ms
         stat = torch.tensor([wall, float(results[:, 10].sum().item()) * N_SAMPLES, ev_ms, float(passes), float(jac), dev_us,
@@ -529,7 +558,7 @@ def single_line(args, model, ctx, steps, warmup, angles, x, rank0_cpu):
         return allstat, results
 
     out = {}
-    for method, name in ((0, "dif"), (1, "bc_dif")):
+    for method, name in ((0, "dif"), (1, "bc_dif")) if args.full else ((0, "dif"),):
         allstat, results = run(method, steps, warmup)
         wall = float(allstat[:, 0].max())  # max over ranks
         evals = float(allstat[:, 1].sum())  # whole job
@@ -624,12 +653,13 @@ def single_line(args, model, ctx, steps, warmup, angles, x, rank0_cpu):
                    "passes_per_fit": head["passes_per_step"]},
         "roofline": roof,
         "fitted_params": head["p"], "sumsq": head["sumsq"],
-        "bc_dif": {k: out["bc_dif"][k] for k in ("value", "ms_per_step", "nfev", "njev", "iters", "reference_passes_per_step", "passes_per_step",
-                                                    "launches_per_step", "avg_launch_us", "launch_timer", "call_us_per_launch", "avg_sweeping_launch_us", "p")},
     }
-    line["bc_dif"]["roofline"] = {k: v for k, v in roofline_of(out["bc_dif"], 1).items()
-                                  if k in ("achieved", "frac", "traffic", "traffic_source", "kernel", "algorithmic_bytes_per_launch", "avg_launch_us",
-                                           "reference_passes_per_launch", "sweeps_per_launch", "frac_by_executed_sweeps", "alu")}
+    if "bc_dif" in out:
+        line["bc_dif"] = {k: out["bc_dif"][k] for k in ("value", "ms_per_step", "nfev", "njev", "iters", "reference_passes_per_step", "passes_per_step",
+                                                        "launches_per_step", "avg_launch_us", "launch_timer", "call_us_per_launch", "avg_sweeping_launch_us", "p")}
+        line["bc_dif"]["roofline"] = {k: v for k, v in roofline_of(out["bc_dif"], 1).items()
+                                      if k in ("achieved", "frac", "traffic", "traffic_source", "kernel", "algorithmic_bytes_per_launch", "avg_launch_us",
+                                               "reference_passes_per_launch", "sweeps_per_launch", "frac_by_executed_sweeps", "alu")}
     rc = 0
     if rank0_cpu:
         base, p_cpu, info_cpu = rank0_cpu["dif"]
@@ -731,7 +761,7 @@ def channels_line(args, model, ctx, steps, warmup, angles, x, K=3):
 
 
 def main_single(args, model):
-    """c2 / c3.  The default run (`python bench.py`: c2 on one GPU) also carries the other BASELINE.json configurations as
+    """c2 / c3.  The full run (`python bench.py --full`: c2 on one GPU) also carries the other BASELINE.json configurations as
     short sub-lines under `configs`: c3 through both entry points, c4 and c5 through dlevmar_dif -- a few steps each, parity
     against single CPU fits (c3) or the CPU fits of the first 64 surfels (c4 / c5) instead of the timed CPU baselines, which
     the explicit `--workload` runs keep."""
@@ -739,8 +769,8 @@ def main_single(args, model):
     rank_env = int(os.environ.get("RANK", "0"))
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     angles, x, truth = synth.make_single(model, N_SAMPLES, seed=synth.SEED + 7919 * rank_env)
-    with_cpu = not args.no_cpu and rank_env == 0 and world_env == 1
-    subs = args.workload == "c2" and args.gpus == 1 and world_env == 1 and not args.headline_only and os.environ.get("BRDF_BENCH_STUB") != "1"
+    with_cpu = args.full and not args.no_cpu and rank_env == 0 and world_env == 1
+    subs = args.full and args.workload == "c2" and args.gpus == 1 and world_env == 1 and not args.headline_only and os.environ.get("BRDF_BENCH_STUB") != "1"
     # CPU legs first, before this process has touched the GPU (they are never inside a timed region either way)
     rank0_cpu = single_cpu_refs(model, angles, x) if with_cpu else {}
     sub_cpu = {}
@@ -751,7 +781,7 @@ def main_single(args, model):
             sub_cpu[wl] = batched_cpu_subset(wl, "dif") if with_cpu else None
     ctx = dist_setup(args)
     torch, dist, rank, world = ctx[0], ctx[1], ctx[2], ctx[3]
-    line, rc = single_line(args, model, ctx, args.steps, args.warmup, angles, x, rank0_cpu)
+    line, rc = single_line(args, model, ctx, args.steps, args.warmup, angles, x, rank0_cpu, args.dump_outputs)
     if rank == 0 and args.channels > 1 and os.environ.get("BRDF_BENCH_STUB") != "1":
         line["channels"] = channels_line(args, model, ctx, args.steps, args.warmup, angles, x, args.channels)
     if rank == 0 and subs:
@@ -792,12 +822,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: CPU baselines and parity against CPU levmar, the "
+                    "dlevmar_bc_dif figures of c2 / c3, the configs[2..4] and three-channel sub-lines of c2 on one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the headline's last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline and parity legs")
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "c4", "c5"],
                     help="c2 (default, the benchmarked configuration): BASELINE.json configs[1] (Ward); c3: configs[2] (Blinn-Phong); "
                          "c4 / c5: configs[3] / [4], the multi-surfel configurations, surfels sharded over the ranks (strong scaling)")
     ap.add_argument("--entry", default="dif", choices=["dif", "bc_dif"], help="entry point for c4 / c5")
-    ap.add_argument("--headline-only", action="store_true", help="c2 on one GPU without the configs[2..4] sub-lines")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: c2 on one GPU without the configs[2..4] sub-lines")
     ap.add_argument("--channels", type=int, default=1, help="c2 / c3: add a line for K colour channels over one set of planes (dlevmar_bc_dif, "
                     "brdf_hip_fit_channels_dev: one shared resident launch) next to the headline")
     ap.add_argument("--surfels", type=int, default=0, help=argparse.SUPPRESS)  # rehearsal / tests: shrink c4 / c5

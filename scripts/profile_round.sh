@@ -11,8 +11,8 @@ run() {  # run <subdir> <rocprofv3 options...> -- <program...>
   local sub=$1; shift
   timeout -k 10 400 rocprofv3 --output-format csv -d $OUT/$sub "$@" > $OUT/$sub.log 2>&1 || { echo "FAILED: $sub"; tail -5 $OUT/$sub.log; exit 1; }
 }
-# the default bench run: configs[1] headline (both entry points) + the configs[2..4] sub-lines -> every fit kernel of the line
-BENCH="python3 bench.py --steps 10 --warmup 2 --no-cpu"
+# the full bench run: configs[1] headline (both entry points) + the configs[2..4] sub-lines -> every fit kernel of the line
+BENCH="python3 bench.py --full --steps 10 --warmup 2 --no-cpu"
 run trace --kernel-trace --stats -- $BENCH
 run pmc_fetch --kernel-trace --pmc FETCH_SIZE -- $BENCH
 run pmc_write --kernel-trace --pmc WRITE_SIZE -- $BENCH

@@ -90,7 +90,7 @@ if len(sys.argv) > 3 and sys.argv[2] == "--traffic-json":
                 kernels[k]["sq_active_inst_valu_per_launch"] = st.mean([x for x in valu_busy[k] if x > 0.05 * max(valu_busy[k])])
                 kernels[k]["sq_wave_cycles_per_launch"] = st.mean([x for x in wave_cyc[k] if x > 0.05 * max(wave_cyc[k])])
     json.dump({"tag": tag, "source_hash": h.hexdigest()[:16],
-               "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc SQ_INSTS_VALU ... in separate passes over `python3 bench.py --steps 10 --warmup 2 --no-cpu` (scripts/profile_round.sh)",
+               "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc SQ_INSTS_VALU ... in separate passes over `python3 bench.py --full --steps 10 --warmup 2 --no-cpu` (scripts/profile_round.sh)",
                "calibration": f"scripts/calib_traffic.py: model_eval_kernel<2> reads 3 x 512 MiB / writes 512 MiB, 8 B per lane coalesced: FETCH_SIZE x {fcorr:.4f}, WRITE_SIZE x {wcorr:.4f}",
                "kernels": kernels}, open(out_path, "w"), indent=1)
     print("wrote", out_path)

@@ -152,3 +152,29 @@ def test_bench_launches_its_own_ranks(tmp_path):
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--workload", "c5", "--no-cpu"], capture_output=True,
                          text=True, env=dict(env, RANK="0", WORLD_SIZE="1"), cwd=ROOT, timeout=600)
     assert bad.returncode != 0 and "WORLD_SIZE" in (bad.stderr + bad.stdout)
+
+
+def test_bench_dumps_the_last_steps_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the rows the last timed step returned (p, info, ret) as float64 .npy files, the same
+    from run to run with the same arguments (fit stubbed as above); past the size budget, a fixed sample of rows and their indices."""
+    import subprocess
+    import sys
+    env = dict(os.environ, BRDF_BENCH_BACKEND="gloo", BRDF_BENCH_STUB="1")
+    env.pop("RANK", None)
+    env.pop("WORLD_SIZE", None)
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5", "--surfels", "37", "--samples", "16",
+                              "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True,
+                             env=env, cwd=ROOT, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+    for name, shape in (("p", (37, 3)), ("info", (37, 10)), ("ret", (37,))):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64 and a.shape == shape and np.array_equal(a, b)
+    import bench
+    rows = {"p": np.arange(3000.0).reshape(1000, 3), "ret": np.arange(1000)}
+    for run in ("c", "d"):
+        bench.dump_outputs(str(tmp_path / run), rows, budget=16000)
+    idx = np.load(tmp_path / "c" / "rows.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "d" / "rows.npy")) and 0 < idx.size < 1000 and np.all(np.diff(idx) > 0)
+    assert sum(f.stat().st_size for f in (tmp_path / "c").iterdir()) <= 16000 + 3 * 128  # (+ the .npy headers)
+    assert np.array_equal(np.load(tmp_path / "c" / "p.npy"), rows["p"][idx.astype(int)])

@@ -960,9 +960,10 @@ def test_host_batch_entry_point_and_null_measurements(gpu):
 def test_compiled_cpp_call_site_links_and_fits(gpu, tmp_path):
     """tests/cpp/dropin_solve_equation.cpp: the reference's SolveEquation call site (its own struct extraData, its
     own BRDFFunc, dlevmar_bc_dif with NULL work/covar) compiled by g++ and LINKED against libbrdf_hip.so in place
-    of liblevmar.a, plus the one registration line.  The application's callback must never run."""
+    of liblevmar.a, plus the one registration line.  The application's callback must never run.  The binary holds the
+    reference's text, so it is built into oracle/_ref/ (by __graft_entry__.build() where the reference exists)."""
     import subprocess
-    exe = os.path.join(HERE, "cpp", "dropin_solve_equation")
+    exe = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "dropin_solve_equation")
     subprocess.run(["make", "-s", "-C", os.path.join(HERE, "cpp"), "dropin_solve_equation"], check=True)
     for model, n in ((1, 16), (1, 5000), (0, 2000)):
         angles, x, _ = synth.make_single(model, n)
