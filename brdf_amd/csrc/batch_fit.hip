@@ -602,6 +602,19 @@ struct BatchScratch {
   int device = -1;
   hipEvent_t last_use = nullptr;
   bool in_use = false;
+  // a host thread that ends gives its block back, on the block's device, once its last batch is done with it
+  ~BatchScratch() {
+    if (!ptr) return;
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    if (cur != device) (void)hipSetDevice(device);
+    if (last_use) {
+      (void)hipEventSynchronize(last_use);
+      (void)hipEventDestroy(last_use);
+    }
+    (void)hipFree(ptr);
+    if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
+  }
 };
 thread_local BatchScratch g_scratch;
 

@@ -2,6 +2,8 @@
 // The kernels themselves (and the file comment that explains the regime) live in resident_fit_impl.h; each (MODEL, METHOD)
 // pair is its own translation unit (resident_inst.hip, compiled with -DRI_PAIR=<model><method>), because hipcc needs 40-60 s
 // per pair and the nine of them used to be one 6.5-minute compile.
+#include <atomic>
+
 #include "resident_fit_impl.h"
 
 namespace brdf {
@@ -72,9 +74,9 @@ bool resident_fit_try(const StreamFitArgs &a, int *ret) {
   default: r = resident_run_22(a, ws, &unavailable); break;
   }
   if (unavailable) {
-    static bool warned = false;
-    if (!warned) fprintf(stderr, "libbrdf_hip: resident single-launch path unavailable (grid not co-resident?); using the launch chain\n");
-    warned = true;
+    static std::atomic<bool> warned{false};  // once per process, also when host threads on several devices get here at once
+    if (!warned.exchange(true))
+      fprintf(stderr, "libbrdf_hip: resident single-launch path unavailable (grid not co-resident?); using the launch chain\n");
     ws.backoff = std::min(1024, std::max(8, ws.backoff * 2));
     ws.skip = ws.backoff;
     if (const char *e = getenv("BRDF_HIP_RESIDENT_BACKOFF")) ws.skip = std::max(0, atoi(e));  // tests

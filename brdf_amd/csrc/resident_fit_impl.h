@@ -45,6 +45,7 @@
 // the grid is not co-resident (or anything else goes wrong) all workgroups drain, the launch ends with ctl->abort set
 // and the host falls back to the launch chain (tests/test_gpu_parity.py exercises that path by sabotage).
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -1340,10 +1341,15 @@ int resident_attempt(const StreamFitArgs &a, RWorkspace &ws, bool *retry_exact, 
   if (const char *e = getenv("BRDF_HIP_RESIDENT_SPIN_MS")) c.spin_ticks = std::max(1LL, atoll(e)) * 100000LL;
   if (const char *e = getenv("BRDF_HIP_RESIDENT_SABOTAGE")) c.sabotage_epoch = atoi(e);  // tests only: forces the fallback
 
-  {  // one workgroup per CU must be able to live there at all (registers, LDS): checked once per kernel
-    static int per_cu = -1;
-    if (per_cu < 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resident_fit_kernel<MODEL, METHOD, FAST, false>, kRThreads, 0) != hipSuccess)
-      per_cu = 0;
+  {  // one workgroup per CU must be able to live there at all (registers, LDS): checked once per kernel (atomic: host
+     // threads on several devices may get here at once)
+    static std::atomic<int> per_cu_once{-1};
+    int per_cu = per_cu_once.load(std::memory_order_relaxed);
+    if (per_cu < 0) {
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resident_fit_kernel<MODEL, METHOD, FAST, false>, kRThreads, 0) != hipSuccess)
+        per_cu = 0;
+      per_cu_once.store(per_cu, std::memory_order_relaxed);
+    }
     if (per_cu < 1) {
       *unavailable = true;
       return 0;

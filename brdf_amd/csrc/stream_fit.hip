@@ -518,6 +518,15 @@ struct Workspace {
     d_dif = nullptr;
     dif_cap = 0;
   }
+  // a host thread that ends gives its blocks back (its fits are synchronous: nothing of them is in flight), on their device
+  ~Workspace() {
+    if (!d_ctx && !d_dif) return;
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    if (device >= 0 && cur != device) (void)hipSetDevice(device);
+    release();
+    if (cur >= 0 && device >= 0 && cur != device) (void)hipSetDevice(cur);
+  }
 };
 thread_local Workspace g_ws;
 

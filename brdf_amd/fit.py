@@ -148,6 +148,44 @@ def fit_batch(method: int, model: int, angles, x, p0, *, lb=None, ub=None, itmax
     return p, info, ret
 
 
+def fit_batch_multi(method: int, model: int, angles, x, p0, *, devices=None, lb=None, ub=None, itmax=100, opts=None):
+    """S independent fits over several GPUs of this process (brdf_hip_fit_batch_multi): HOST arrays angles [S,3,n], x [S,n],
+    p0 [S,3] (not modified).  `devices`: HIP ordinals, one contiguous shard of ceil(S/len) fits each (dist.shard_range; an
+    ordinal may repeat); None: every visible device once.  Returns numpy (p [S,3], info [S,10], ret [S] int32), bit-identical
+    to one device's brdf_hip_fit_batch.  The GIL is released during the call."""
+    angles = np.ascontiguousarray(angles, dtype=np.float64)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    _require(x.ndim == 2, "x must be [S, n]")
+    S, n = x.shape
+    _require(angles.shape == (S, 3, n), "angles must be [S, 3, n]")
+    p = np.array(p0, dtype=np.float64, order="C").reshape(-1)
+    _require(p.size == 3 * S, "p0 must be [S, 3]")
+    p = p.reshape(S, 3)
+    info = np.zeros((S, 10))
+    ret = np.zeros(S, dtype=np.int32)
+    lb_a, ub_a, op_a = _f64(lb, 3), _f64(ub, 3), _f64(opts, 5)
+    dev_list, ndev = None, 0
+    if devices is not None:
+        devices = [int(d) for d in devices]
+        dev_list, ndev = (C.c_int * max(1, len(devices)))(*devices), len(devices)
+    rc = lib.brdf_hip_fit_batch_multi(method, model, _dptr(angles), _dptr(x), S, n, _dptr(p), _dptr(lb_a), _dptr(ub_a), itmax,
+                                      _dptr(op_a), _dptr(info), ret.ctypes.data_as(C.POINTER(C.c_int)), dev_list, ndev)
+    if rc < 0:
+        raise RuntimeError(f"brdf_hip_fit_batch_multi failed: {last_error()}")
+    return p, info, ret
+
+
+def last_multi_stats() -> list:
+    """per shard of this thread's last fit_batch_multi(): device, first fit, fit count and upload / fit / download
+    milliseconds as the device's stream saw them"""
+    out = []
+    dev, first, count, ms = C.c_int(0), C.c_longlong(0), C.c_longlong(0), (C.c_double * 3)()
+    while lib.brdf_hip_last_multi_stats(len(out), C.byref(dev), C.byref(first), C.byref(count), ms) == 0:
+        out.append({"device": dev.value, "first": first.value, "count": count.value, "upload_ms": ms[0], "fit_ms": ms[1],
+                    "download_ms": ms[2]})
+    return out
+
+
 def model_eval(model: int, angles, p):
     """hx = model(p; samples) on the device (kernel K1 alone).  angles: CUDA float64 [3,n]."""
     import torch

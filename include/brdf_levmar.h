@@ -11,6 +11,14 @@
  * `_dev`, pointers are HOST pointers.  Errors never call exit(): they return LM_ERROR (-1) after a
  * message on stderr, as the reference does for its own argument errors (lm_core.c:502-505,
  * lmbc_core.c:440-461), and brdf_hip_last_error() returns the text.
+ *
+ * Host threads.  Every entry point works on the calling thread's current HIP device (brdf_hip_fit_batch_multi
+ * excepted: it runs on the devices it is given, from threads of its own) and keeps its buffers per host thread, so
+ * threads on different devices are independent.  Threads that share a device get correct results; but two single fits
+ * that both take the resident single-launch regime (brdf_hip_fit_dev, the drop-in calls, the fits of a batch with
+ * n > 4096; up to #CUs * 4096 samples) can fail to be co-resident, wait out their spin budget and fall back to the
+ * launch chain with a warning on stderr: serialise single fits per device.  The brdf_hip_last_* getters report the
+ * calling thread's last call.  Model registration (brdf_hip_register_model) is process-wide and locked.
  */
 #ifndef BRDF_LEVMAR_H
 #define BRDF_LEVMAR_H
@@ -186,6 +194,34 @@ int brdf_hip_fit_batch_dev(int method, int model, const double *d_angles, const 
 int brdf_hip_fit_batch(int method, int model, const double *angles, const double *x, int S, int n,
                        double *p, const double *lb, const double *ub, int itmax, const double *opts,
                        double *info, int *ret);
+
+/* brdf_hip_fit_batch over several GPUs: the S fits are split into ndev contiguous shards, shard k going to device
+ * devices[k] (HIP ordinals of this process; a device may be listed more than once, devices == NULL: every visible
+ * device once, ndev ignored).  Shard k holds fits [k*ceil(S/ndev), ...) -- the rule of brdf_amd/dist.py shard_range;
+ * trailing shards may be short or empty.  Arguments and return value otherwise as brdf_hip_fit_batch: HOST pointers,
+ * per-fit p/info/ret land in the caller's arrays, the return value is the number of fits that ended in LM_ERROR, or
+ * LM_ERROR itself on bad arguments or a HIP failure (message in brdf_hip_last_error() of the calling thread).  Every
+ * fit's p, info and ret are bit-identical to brdf_hip_fit_batch on one device.  The caller's current device is left as
+ * it was, and so are the calling thread's brdf_hip_last_fit_* counters.
+ *   - Arguments (null angles/x/p, S or n <= 0, an unknown model/method, ndev < 1 or > 64 with a list) are checked
+ *     before any HIP call; device ordinals against hipGetDeviceCount before anything is uploaded.
+ *   - One host thread per DISTINCT listed device, started by the call and joined before it returns: it creates its
+ *     own stream and runs that device's shards one after the other in list order (upload, brdf_hip_fit_batch_dev,
+ *     download).  A device listed twice never runs two shards of one call at the same time.  The buffers and the
+ *     library's per-thread workspaces of a call are allocated by it and freed before it returns.
+ *   - Errors: the first failed shard (in list order) is named as "device D, fits [a, b): <message>".  The other
+ *     devices still finish their shards.  Results are downloaded only after a shard's fit succeeded: the rows of
+ *     p / info / ret of a shard whose upload or fit failed, and of the later shards of the same device, are left as
+ *     the caller passed them.
+ *   - Two host threads that call brdf_hip_fit_batch_multi at the same time are serialised (one process-wide lock
+ *     around the call). */
+int brdf_hip_fit_batch_multi(int method, int model, const double *angles, const double *x, int S, int n, double *p,
+                             const double *lb, const double *ub, int itmax, const double *opts, double *info, int *ret,
+                             const int *devices, int ndev);
+/* shard `shard` of this thread's most recent brdf_hip_fit_batch_multi: its device, first fit, fit count, and
+ * milliseconds of upload / fit / download as that device's stream saw them (HIP events; 0 for a phase that did not
+ * run, e.g. an empty shard); returns 0, or LM_ERROR if `shard` is out of range */
+int brdf_hip_last_multi_stats(int shard, int *device, long long *first, long long *count, double *ms3);
 
 /* hx[i] = model(p; sample i) for device-resident planes; d_hx DEVICE pointer, p HOST pointer. */
 int brdf_hip_model_eval_dev(int model, const double *d_angles, int n, const double *p, double *d_hx,
