@@ -1,0 +1,133 @@
+"""Seeded edge-of-domain fit problems: the fits that real 8-bit captures take and brdf_amd/synth.py never makes.
+
+synth.py draws cosines from [0.05, 1) and truths well inside [0,100]^3, so every fit it makes is well posed and ends
+inside the box.  The families below end ON the box (an active bound), start on it, see black or saturated pixels, reach
+grazing and unit cosines, or hold a cosine <= 0 in the plane the model raises to a power (the fast path's fallback).
+Everything is generated from synth.uniform (counter-based, seeded per family), so a problem is reproducible from
+(family, model, n, index) alone.  CPU only: used by the oracle tests and the GPU tests alike.
+
+    make(family, model, n, index) -> (angles[3, n], x[n], p0[3], lb[3], ub[3])      float64, C-contiguous
+"""
+from __future__ import annotations
+
+import zlib
+
+import numpy as np
+
+from brdf_amd import synth
+
+# family -> models it applies to
+FAMILIES = {
+    "diffuse_only": (0, 1, 2),      # ks = 0 in the truth (slightly below, so the unconstrained optimum is < 0): ks ends on lb
+    "shiny_beyond_box": (0, 1),     # exponent 300, ub 100: n ends on ub
+    "ward_mirror": (2,),            # alpha 0.004, lb alpha 0.01: alpha ends on lb
+    "tight_box": (0, 1, 2),         # ub below the truth in all three components
+    "high_lb": (0, 1, 2),           # lb above the truth in all three components
+    "dark": (0, 1, 2),              # black pixel: noise around 0, clipped at 0
+    "saturated": (0, 1, 2),         # x == 255/255
+    "quantised": (0, 1, 2),         # 8-bit round(clip(x) * 255) / 255
+    "grazing": (0, 1, 2),           # cosines log-uniform down to 1e-4, some exactly 1.0
+    "start_on_bound": (0, 1, 2),    # p0 on lb (SingleBRDF's (0,0,0) for Phong / Blinn-Phong)
+    "nonpositive": (0, 1),          # cosines 0.0 (and, for odd index // 2, negative) in the plane raised to a power
+}
+BOUND_FAMILIES = ("diffuse_only", "shiny_beyond_box", "ward_mirror", "tight_box", "high_lb", "dark")
+BOX_FREE = ("dark", "saturated", "quantised", "grazing", "nonpositive")  # meaningful for dlevmar_dif / dlevmar_der too
+
+
+def _u(family: str, model: int, n: int, index: int, stream: int) -> np.ndarray:
+    seed = synth.SEED ^ (zlib.crc32(family.encode()) << 16) ^ (model << 8)
+    i = np.arange(n, dtype=np.uint64)
+    return synth.uniform(seed, (np.uint64(index) * np.uint64(8) + np.uint64(stream)) * np.uint64(n) + i)
+
+
+def power_plane(model: int) -> int:
+    """the plane the model raises to the power p[2]: cos(R.V) for Phong, cos(N.H) for Blinn-Phong"""
+    return {0: 2, 1: 1}[model]
+
+
+def truth(model: int) -> np.ndarray:
+    return np.array(synth.TRUTH[model], dtype=np.float64)
+
+
+def make(family: str, model: int, n: int, index: int = 0):
+    if model not in FAMILIES[family]:
+        raise ValueError(f"family {family} does not apply to model {model}")
+    angles = np.stack([0.05 + 0.95 * _u(family, model, n, index, k) for k in range(3)])
+    noise = 0.01 * (_u(family, model, n, index, 3) - 0.5)
+    lb, ub = (np.array(b, dtype=np.float64) for b in synth.bounds(model))
+    p0 = np.array(synth.P0[model], dtype=np.float64)
+    t = truth(model)
+
+    if family == "diffuse_only":
+        t[1] = -0.05  # the unconstrained optimum has ks < 0: the box holds ks on 0
+    elif family == "shiny_beyond_box":
+        t = np.array([0.2, 0.9, 300.0])
+        k = power_plane(model)
+        angles[k, ::2] = 1.0 - 0.02 * _u(family, model, n, index, 4)[::2]  # half the lobe samples near the peak
+    elif family == "ward_mirror":
+        t = np.array([0.35, 0.25, 0.004])
+        angles[1, ::3] = 1.0 - 2e-5 * _u(family, model, n, index, 4)[::3]  # a third of cos(N.H) inside the narrow lobe
+    elif family == "tight_box":
+        ub = t * 0.5
+    elif family == "high_lb":
+        lb = t * 1.5
+        ub = np.maximum(ub, lb * 2.0)
+    elif family == "grazing":
+        low = 10.0 ** (-4.0 + 3.0 * _u(family, model, n, index, 5))  # log-uniform in [1e-4, 1e-1)
+        for k in range(3):
+            angles[k, k::3] = low[k::3]
+            angles[k, (k + 1)::7] = 1.0
+    elif family == "start_on_bound":
+        p0 = lb.copy()
+    elif family == "nonpositive":
+        k = power_plane(model)
+        angles[k, 1::max(2, n // 4)] = 0.0
+        if (index // 2) % 2 == 1:
+            angles[k, 0] = -0.25
+        p0[2] = 1.0 if index % 2 == 0 else 1.5  # integral and non-integral starting exponent
+
+    x = synth.model_value(model, t, angles[0], angles[1], angles[2])
+    if family == "dark":
+        x = np.clip(noise, 0.0, None)
+    elif family == "saturated":
+        x = np.full(n, 255.0 / 255.0)
+    elif family == "quantised":
+        x = np.round(np.clip(x + noise, 0.0, 1.0) * 255.0) / 255.0
+    else:
+        x = x + noise
+    return (np.ascontiguousarray(angles), np.ascontiguousarray(x, dtype=np.float64), p0, lb, ub)
+
+
+def cases(models=(0, 1, 2), families=None):
+    """(family, model) pairs in a fixed order"""
+    fams = FAMILIES if families is None else families
+    return [(f, m) for f in fams for m in models if m in FAMILIES[f]]
+
+
+def active_set(p, lb, ub) -> tuple:
+    """components exactly on a bound: (j, 'lb' | 'ub')"""
+    return tuple((j, "lb" if p[j] == lb[j] else "ub") for j in range(3) if p[j] == lb[j] or p[j] == ub[j])
+
+
+def indices(family: str):
+    """problem indices per family: nonpositive has four (zeros / zeros and a negative cosine x integral / non-integral start)"""
+    return (0, 1, 2, 3) if family == "nonpositive" else (0, 1)
+
+
+def methods(family: str):
+    """dlevmar_bc_dif / bc_der everywhere; dlevmar_dif / der where the family does not depend on the box"""
+    return (1, 2, 0, 3) if family in BOX_FREE else (1, 2)
+
+
+FIXTURE_N = (5, 16, 64, 1000)
+
+
+def fixture_cases():
+    """(family, model, method, n, index) of tests/golden/brdf_edge_fits.json, in its order"""
+    return [(f, m, meth, n, i) for f, m in cases() for meth in methods(f) for n in FIXTURE_N for i in indices(f)]
+
+
+def fit_args(family: str, model: int, n: int, index: int = 0):
+    """(angles, x, p0, itmax, opts, lb, ub): the positional arguments of tests.oracle_libs.brdf_fit after (which, method, model)"""
+    angles, x, p0, lb, ub = make(family, model, n, index)
+    return angles, x, p0, synth.ITMAX, synth.OPTS, lb, ub

@@ -12,6 +12,9 @@
                    target; only OpenCV's CV_PI literal is supplied) -- this is what pins the model values.  Ward is
                    build-defined: from the restated callback.
   The BRDF fits of models 0 / 1 are driven by that same `ref_BRDFFunc` (oracle/ref_shim.c).
+  brdf_edge_fits.json the reference's fits on the edge-of-domain families of tests/edge_problems.py (active bounds, black and
+                   saturated pixels, grazing and non-positive cosines, starts on the box): one compact row per fit,
+                   [family, model, method, n, index, ret, p[3], info[10]] (inputs regenerated from the family's seed).
 """
 import ctypes as C
 import json
@@ -24,6 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from brdf_amd import synth  # noqa: E402
 from tests import oracle_libs as L  # noqa: E402
+from tests import edge_problems as E  # noqa: E402
 from tests.kat_problems import PROBLEMS, OPTS, SOPTS, SPROBLEMS, run_problem, run_sproblem  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -42,6 +46,15 @@ def main():
                              "info": [float.hex(v) for v in info]})
     json.dump({"generator": "brdf_amd.synth.make_single(model, n), seed %d" % synth.SEED, "fits": fits},
               open(os.path.join(HERE, "brdf_fits.json"), "w"), indent=1)
+
+    edge = [[fam, model, method, n, idx, int(r), [float.hex(v) for v in p], [float.hex(v) for v in info]]
+            for fam, model, method, n, idx in E.fixture_cases()
+            for r, p, info in [L.brdf_fit("ref", method, model, *E.fit_args(fam, model, n, idx))]]
+    with open(os.path.join(HERE, "brdf_edge_fits.json"), "w") as fh:
+        fh.write('{"generator": "tests.edge_problems.make(family, model, n, index)", "itmax": %d, "opts": %s, "fits": [\n'
+                 % (synth.ITMAX, json.dumps([float.hex(v) for v in synth.OPTS])))
+        fh.write(",\n".join(json.dumps(row, separators=(",", ":")) for row in edge))
+        fh.write("\n]}\n")
 
     kats = []
     for pid, pr in PROBLEMS.items():
@@ -66,7 +79,7 @@ def main():
             vals.append({"model": model, "p": list(p), "source": "ref_BRDFFunc (brdfdata.cpp:962-989 compiled in place)" if model < 2
                          else "oracle/brdf_models_oracle.c (Ward is build-defined)", "hx": [float.hex(v) for v in hx]})
     json.dump({"n": 64, "values": vals}, open(os.path.join(HERE, "model_values.json"), "w"), indent=1)
-    print("wrote", len(fits), "fits,", len(kats), "kats,", len(vals), "model value sets")
+    print("wrote", len(fits), "fits,", len(edge), "edge fits,", len(kats), "kats,", len(vals), "model value sets")
 
 
 if __name__ == "__main__":
