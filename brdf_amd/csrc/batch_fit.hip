@@ -16,7 +16,7 @@
 
 #include "../../include/brdf_levmar.h"
 #include "batch_fit.h"
-#include "stream_fit.h"
+#include "fit_host.h"
 
 namespace brdf {
 
@@ -620,15 +620,6 @@ thread_local BatchScratch g_scratch;
 
 }  // namespace
 
-#define HIP_OK(call)                                                                  \
-  do {                                                                                \
-    hipError_t e_ = (call);                                                           \
-    if (e_ != hipSuccess) {                                                           \
-      set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return kLmError;                                                                \
-    }                                                                                 \
-  } while (0)
-
 namespace {
 
 using RowsFn = void (*)(BatchCtx, int *);
@@ -815,7 +806,7 @@ int batch_fit_enqueue(const BatchFitArgs &a) {
   if ((a.method == 1 || a.method == BRDF_METHOD_BC_DER) && a.lb && a.ub)
     for (int i = 0; i < kM; ++i)
       if (a.lb[i] > a.ub[i]) {  // lmbc_core.c:451-454
-        set_error("dlevmar_bc_dif(): at least one lower bound exceeds the upper one");
+        set_bad_input_error("dlevmar_bc_dif", 2, a.n, kM);
         return kLmError;
       }
   (void)hipGetLastError();

@@ -15,7 +15,7 @@
 
 #include "../../include/brdf_levmar.h"
 #include "batch_fit.h"
-#include "stream_fit.h"
+#include "fit_host.h"
 
 namespace brdf {
 int generic_fit_run(int method, void (*func)(double *, double *, int, int, void *),
@@ -140,7 +140,7 @@ int host_fit(int method, const char *who, model_func_t func, double *p, double *
     return LM_ERROR;
   }
   if (n < m) {  // lm_core.c:502-505, lmbc_core.c:440-443
-    set_error("%s(): cannot solve a problem with fewer measurements [%d] than unknowns [%d]", who, n, m);
+    set_bad_input_error(who, 1, n, m);
     return LM_ERROR;
   }
   if (!adata || !p) {

@@ -338,15 +338,6 @@ __global__ __launch_bounds__(kRThreads) void channels_fit_kernel(ChannelsCtx ctx
       // compiler, every sample re-read them one by one -- ten ds_reads and nine waits per Jacobian row; held in registers for the
       // whole sweep, they push the sixteen resident samples' registers into scratch: 229-425 spilled VGPRs in every variant tried).
       auto sweep = [&](auto &&load, auto &&body) {
-#ifdef BRDF_EXP_CHANNEL_SCALAR
-        const auto u = scalar_copy(load());
-#pragma unroll
-        for (int k = 0; k < kRSpt; ++k)
-          if (k < nk) {
-            body(u, 0, k);
-            body(u, 1, k);
-          }
-#else
 #pragma unroll
         for (int k = 0; k < kRSpt; ++k)
           if (k < nk) {
@@ -355,7 +346,6 @@ __global__ __launch_bounds__(kRThreads) void channels_fit_kernel(ChannelsCtx ctx
             body(u, 0, k);
             body(u, 1, k);
           }
-#endif
       };
       switch (kind) {
       case RQ_EVAL:
@@ -484,217 +474,21 @@ __global__ __launch_bounds__(kRThreads) void channels_fit_kernel(ChannelsCtx ctx
 #endif
 }
 
-// ---------------------------------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------------------------------
-struct ChannelsArgs {
-  int method, model;  // method: 1 dlevmar_bc_dif, 2 dlevmar_bc_der with the model's analytic Jacobian (BRDF_METHOD_*)
-  const double *d_angles;
-  const double *d_x[kMaxChannels];
-  int n, K;
-  double *p;  // [K][3] in/out
-  const double *lb, *ub, *dscl;
-  int itmax;
-  const double *opts;
-  double *info, *covar;  // [K][10], [K][9] or null
-  hipStream_t stream;
+// what an instance exports: a host function that tells its kernels' addresses (the host side that launches them is channels_fit.hip)
+using ChannelsKernelFn = void (*)(ChannelsCtx);
+struct ChannelsKernels {
+  ChannelsKernelFn kernel[2];  // [kFastPath], [kExactPath] (null for Ward, which has no exact path)
 };
-
-struct CWorkspace {
-  int device = -1, cus = 0;
-  char *d_block = nullptr;  // ctl | per channel: rows | group rows
-  Mailbox *h_mbox = nullptr, *d_mbox = nullptr;  // [kMaxChannels]
-  static constexpr size_t off_rows = sizeof(ResidentCtl);
-  static constexpr size_t chan_bytes = sizeof(u64) * (kRowsGranules + kGroupsGranules);
-  static constexpr size_t block_bytes = off_rows + kMaxChannels * chan_bytes;
-  unsigned tag_base[kMaxChannels] = {0, 0, 0};
-  unsigned launches = 0;
-  FitStats stats[kMaxChannels] = {};
-  double launch_us = 0.0;
-  LaunchTimer timer;
-  int backoff = 0, skip = 0;
-  void release() {
-    if (!d_block && !h_mbox) return;
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    if (device >= 0 && cur != device) (void)hipSetDevice(device);
-    (void)hipDeviceSynchronize();
-    if (d_block) (void)hipFree(d_block);
-    if (h_mbox) (void)hipHostFree(h_mbox);
-    if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
-    d_block = nullptr;
-    h_mbox = d_mbox = nullptr;
-  }
-  ~CWorkspace() { release(); }
-  int ensure(int dev) {
-    if (device == dev && d_block) return 0;
-    release();
-    device = dev;
-    hipDeviceProp_t prop;
-    HIP_OK(hipGetDeviceProperties(&prop, dev));
-    cus = prop.multiProcessorCount;
-    HIP_OK(hipMalloc(&d_block, block_bytes));
-    HIP_OK(hipMemset(d_block, 0, block_bytes));
-    for (int c = 0; c < kMaxChannels; ++c) tag_base[c] = 0;
-    launches = 0;
-    HIP_OK(hipHostMalloc(&h_mbox, sizeof(Mailbox) * kMaxChannels, hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_OK(hipHostGetDevicePointer((void **)&d_mbox, h_mbox, 0));
-    return 0;
-  }
-};
-
 template <int MODEL, bool FAST>
-int channels_attempt(const ChannelsArgs &a, CWorkspace &ws, bool *retry_exact, bool *unavailable) {
-  using Machine = BcMachine<kM>;
-  *retry_exact = *unavailable = false;
-  const int G = (int)std::min<long long>(ws.cus, std::max<long long>(1, ((long long)a.n + 1023) / 1024));  // (the single fit's grid)
-  for (int c = 0; c < a.K; ++c) {  // the entry point's argument checks and warnings, per channel (the kernel starts its own machines)
-    Machine m;
-    memset(&m, 0, sizeof m);
-    m.start(a.p + c * kM, a.n, a.lb, a.ub, a.dscl, a.itmax, a.opts, a.covar != nullptr, pg_candidates());
-    if (m.h.req.kind == RQ_DONE) {
-      switch (m.c.bad_input) {
-      case 1: set_error("dlevmar_bc_dif(): cannot solve a problem with fewer measurements [%d] than unknowns [%d]", a.n, kM); break;
-      case 2: set_error("dlevmar_bc_dif(): at least one lower bound exceeds the upper one"); break;
-      default: set_error("dlevmar_bc_dif(): scaling constants should be positive"); break;
-      }
-      return kLmError;
-    }
-    if (FAST || !brdf_fast_path_enabled())
-      for (int i = 0; i < kM; ++i)  // same warning as lmbc_core.c:516-520
-        if (m.c.infeasible_mask & (1 << i))
-          fprintf(stderr, "Warning: component %d of starting point not feasible in dlevmar_bc_dif()! [%g projected to %g]\n", i,
-                  m.c.p_start[i], m.h.p[i]);
-  }
-  memset(ws.h_mbox, 0, sizeof(Mailbox) * kMaxChannels);
-  unsigned top = 0;
-  for (int c = 0; c < kMaxChannels; ++c) top = std::max(top, ws.tag_base[c]);
-  if (top > 0xF0000000u || ws.launches > 0xF0000000u) {  // tag / launch-id space nearly used up: start over from zeroed tables
-    HIP_OK(hipMemsetAsync(ws.d_block, 0, CWorkspace::block_bytes, a.stream));
-    for (int c = 0; c < kMaxChannels; ++c) ws.tag_base[c] = 0;
-    ws.launches = 0;
-  }
-  ChannelsCtx c;
-  c.c0 = a.d_angles;
-  c.c1 = a.d_angles + a.n;
-  c.c2 = a.d_angles + 2 * (size_t)a.n;
-  for (int k = 0; k < kMaxChannels; ++k) c.x[k] = a.d_x[k < a.K ? k : 0];
-  c.ctl = reinterpret_cast<ResidentCtl *>(ws.d_block);
-  c.rows = reinterpret_cast<u64 *>(ws.d_block + CWorkspace::off_rows);
-  c.groups = c.rows + kMaxChannels * kRowsGranules;
-  c.launch_id = ++ws.launches;  // nonzero, different for every launch on this workspace
-  for (int k = 0; k < kMaxChannels; ++k)
-    for (int i = 0; i < kM; ++i) c.p0[k][i] = a.p[(k < a.K ? k : 0) * kM + i];
-  for (int i = 0; i < kM; ++i) {
-    c.lb[i] = a.lb ? a.lb[i] : 0.0;
-    c.ub[i] = a.ub ? a.ub[i] : 0.0;
-    c.dscl[i] = a.dscl ? a.dscl[i] : 1.0;
-  }
-  for (int i = 0; i < 5; ++i) c.opts[i] = a.opts ? a.opts[i] : 0.0;
-  c.itmax = a.itmax;
-  c.has_opts = a.opts != nullptr;
-  c.has_lb = a.lb != nullptr;
-  c.has_ub = a.ub != nullptr;
-  c.has_dscl = a.dscl != nullptr;
-  c.want_covar = a.covar != nullptr;
-  c.multi = pg_candidates();
-  c.analytic = a.method == 2 ? 1 : 0;
-  c.spec_jac = bc_spec_jac_enabled() ? 1 : 0;
-  c.mbox = ws.d_mbox;
-  c.n = a.n;
-  c.K = a.K;
-  for (int k = 0; k < kMaxChannels; ++k) c.tag_base[k] = ws.tag_base[k];
-  c.spin_ticks = kSpinBudgetTicks;
-  c.replicas = kReplicas;
-  if (const char *e = getenv("BRDF_HIP_RESIDENT_REPLICAS")) c.replicas = std::min(kReplicas, std::max(1, atoi(e)));
-  if (const char *e = getenv("BRDF_HIP_RESIDENT_SPIN_MS")) c.spin_ticks = std::max(1LL, atoll(e)) * 100000LL;
-  c.sabotage_epoch = -1;
-  if (const char *e = getenv("BRDF_HIP_RESIDENT_SABOTAGE")) c.sabotage_epoch = atoi(e);  // tests only: forces the fallback
-  {  // one workgroup per CU must be able to live there at all (registers, LDS): checked once per kernel
-    static int per_cu = -1;
-    if (per_cu < 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, channels_fit_kernel<MODEL, FAST>, kRThreads, 0) != hipSuccess) per_cu = 0;
-    if (per_cu < 1) {
-      *unavailable = true;
-      return 0;
-    }
-  }
-  const auto t0 = std::chrono::steady_clock::now();
-  ws.timer.before(a.stream);
-  hipLaunchKernelGGL((channels_fit_kernel<MODEL, FAST>), dim3(G), dim3(kRThreads), 0, a.stream, c);
-  HIP_OK(hipGetLastError());
-  ws.timer.after(a.stream);
-  {  // wait on the pinned mailboxes; the launch always terminates (bounded spins), which hipStreamQuery reports
-    auto all_done = [&] {
-      for (int k = 0; k < a.K; ++k)
-        if (!*(volatile int *)&ws.h_mbox[k].done) return false;
-      return true;
-    };
-    for (unsigned spins = 0; !all_done(); ++spins)
-      if ((spins & 0x3FFu) == 0x3FFu && hipStreamQuery(a.stream) != hipErrorNotReady) break;
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    if (!all_done()) {
-      HIP_OK(hipStreamSynchronize(a.stream));
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    }
-    if (!all_done()) {  // aborted: not co-resident / spin budget exhausted.  Tags of unknown epochs were stored: start over
-      (void)hipMemsetAsync(ws.d_block, 0, CWorkspace::block_bytes, a.stream);
-      for (int k = 0; k < kMaxChannels; ++k) ws.tag_base[k] = 0;
-      *unavailable = true;
-      return 0;
-    }
-  }
-  ws.launch_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-#ifdef BRDF_STAMPS
-  HIP_OK(hipStreamSynchronize(a.stream));  // (the sweeping waves write their stamps when they leave, after the last channel's result)
-#endif
-  int worst = 0;
-  bool bad_domain = false;
-  for (int k = 0; k < a.K; ++k) {
-    const Mailbox &mb = ws.h_mbox[k];
-    ws.tag_base[k] += (unsigned)mb.passes + 2u;
-    bad_domain = bad_domain || (FAST && mb.domain_bad);
-  }
-  if (bad_domain) {
-    *retry_exact = true;
-    return 0;
-  }
-  for (int k = 0; k < a.K; ++k) {
-    const Mailbox &mb = ws.h_mbox[k];
-    for (int i = 0; i < kM; ++i) a.p[k * kM + i] = mb.p[i];
-    if (a.info)
-      for (int i = 0; i < kInfoSz; ++i) a.info[k * kInfoSz + i] = mb.info[i];
-    if (a.covar)
-      for (int i = 0; i < kM * kM; ++i) a.covar[k * kM * kM + i] = mb.covar[i];
-    ws.stats[k].passes = mb.passes;
-    ws.stats[k].launches = 1;
-    ws.stats[k].jac_passes = mb.n_jac;
-    ws.stats[k].eval_passes = mb.n_eval;
-    ws.stats[k].device_us = (double)(mb.t_last - mb.t_first) / 100.0;
-    ws.stats[k].kernel_us = k == 0 ? ws.timer.elapsed_us() : ws.stats[0].kernel_us;  // (the shared launch's)
-    for (int i = 0; i < 8; ++i) ws.stats[k].stamps[i] = mb.stamps[i];
-    if (mb.ret < 0) worst = kLmError;
-  }
-  return worst;
-}
-
-template <int MODEL>
-int channels_run_m(const ChannelsArgs &a, CWorkspace &ws, bool *unavailable) {
-  bool retry = false;
-  double keep[kMaxChannels * kM];
-  for (int i = 0; i < a.K * kM; ++i) keep[i] = a.p[i];
-  if (brdf_fast_path_enabled() || MODEL == MODEL_WARD) {
-    const int ret = channels_attempt<MODEL, true>(a, ws, &retry, unavailable);
-    if (!retry || *unavailable) return ret;
-    for (int i = 0; i < a.K * kM; ++i) a.p[i] = keep[i];
-  }
-  if constexpr (MODEL != MODEL_WARD)
-    return channels_attempt<MODEL, false>(a, ws, &retry, unavailable);
+constexpr ChannelsKernelFn channels_kernel() {  // (null for Ward's exact path: see resident_kernel())
+  if constexpr (FAST || MODEL != MODEL_WARD)
+    return channels_fit_kernel<MODEL, FAST>;
   else
-    return kLmError;
+    return nullptr;
 }
 
 // one translation unit per MODEL: channels_inst.hip
 #define BRDF_CHANNELS_INSTANCE(MODEL_, NAME_) \
-  int channels_run_##NAME_(const ChannelsArgs &a, CWorkspace &ws, bool *unavailable) { return channels_run_m<MODEL_>(a, ws, unavailable); }
+  ChannelsKernels channels_kernels_##NAME_() { return {{channels_kernel<MODEL_, true>(), channels_kernel<MODEL_, false>()}}; }
 
 }  // namespace brdf

@@ -21,7 +21,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "stream_fit.h"
+#include "fit_host.h"
 
 namespace brdf {
 
@@ -218,15 +218,6 @@ __global__ __launch_bounds__(kGenThreads) void gen_pass_kernel(GenArgs<Real> a) 
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
-#define HIP_OK(call)                                                                  \
-  do {                                                                                \
-    hipError_t e_ = (call);                                                           \
-    if (e_ != hipSuccess) {                                                           \
-      set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return kLmError;                                                                \
-    }                                                                                 \
-  } while (0)
-
 template <class Real>
 using user_func_of = void (*)(Real *p, Real *hx, int m, int n, void *adata);
 template <class Real>
@@ -260,25 +251,16 @@ int generic_run(user_func_of<Real> func, user_jacf_of<Real> jacf, Real *p, Real 
     mach.start(p, n, itmax, opts, covar != nullptr);
   if constexpr (METHOD == 1) mach.c.analytic_jac = jacf ? 1 : 0;
   if (mach.h.req.kind == RQ_DONE) {
-    if constexpr (METHOD == 1) {
-      if (mach.c.bad_input == 2) {
-        set_error("dlevmar_bc_dif(): at least one lower bound exceeds the upper one");
-        return kLmError;
-      }
-      if (mach.c.bad_input == 3) {
-        set_error("dlevmar_bc_dif(): scaling constants should be positive");
-        return kLmError;
-      }
-    }
-    set_error("%clevmar_%s(): cannot solve a problem with fewer measurements [%d] than unknowns [%d]", sizeof(Real) == 4 ? 's' : 'd',
-              METHOD == 0 ? "dif" : (METHOD == 1 ? "bc_dif" : "der"), n, M);
+    int bad = 1;
+    if constexpr (METHOD == 1) bad = mach.c.bad_input;
+    char who[24];  // (the texts about the box and the scaling constants say dlevmar_bc_dif in either precision)
+    snprintf(who, sizeof who, "%clevmar_%s", sizeof(Real) == 4 ? 's' : 'd', METHOD == 0 ? "dif" : (METHOD == 1 ? "bc_dif" : "der"));
+    set_bad_input_error(bad == 1 ? who : "dlevmar_bc_dif", bad, n, M);
     return kLmError;
   }
   if constexpr (METHOD == 1)
     for (int i = 0; i < M; ++i)
-      if (mach.c.infeasible_mask & (1 << i))
-        fprintf(stderr, "Warning: component %d of starting point not feasible in dlevmar_bc_dif()! [%g projected to %g]\n", i,
-                mach.c.p_start[i], mach.h.p[i]);
+      if (mach.c.infeasible_mask & (1 << i)) warn_start_projected(i, mach.c.p_start[i], mach.h.p[i]);
 
   // device buffers: x | hx | wrk | aux (2M planes) | jac (n*M) | out
   const size_t need = (size_t)n * (3 + 2 * M + M) + kGenSums;

@@ -45,7 +45,7 @@ __device__ __forceinline__ bool lane_phase_enter(int x) {
 #define LM_PHASE_ENTER(X) lane_phase_enter((int)(X))
 #endif
 #include "batch_fit.h"
-#include "stream_fit.h"
+#include "fit_host.h"
 
 namespace brdf {
 
@@ -284,15 +284,6 @@ __global__ __launch_bounds__(kWave, W) void lane_fit_kernel(BatchCtx ctx, int *q
   if (lane < 32) atomicAdd((unsigned long long *)&g_lane_phase[lane], (unsigned long long)lp_acc[lane]);
 #endif
 }
-
-#define HIP_OK(call)                                                                  \
-  do {                                                                                \
-    hipError_t e_ = (call);                                                           \
-    if (e_ != hipSuccess) {                                                           \
-      set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return kLmError;                                                                \
-    }                                                                                 \
-  } while (0)
 
 namespace {
 using LaneFn = void (*)(BatchCtx, int *);

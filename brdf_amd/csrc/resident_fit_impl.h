@@ -1,5 +1,5 @@
 #pragma once
-// resident_fit_impl.h -- kernels and per-instance host code of the resident regime; compiled once per (MODEL, METHOD) by
+// resident_fit_impl.h -- kernels of the resident regime (their host side: resident_fit.hip); compiled once per (MODEL, METHOD) by
 // resident_inst.hip (nine translation units: one 6.5-minute compile became nine of under a minute, in parallel).
 //
 // "resident" regime: ONE launch per fit, the samples never leave the chip.
@@ -44,12 +44,6 @@
 // dispatch order or XCD placement (fold order = workgroup index).  Every spin is bounded by a wall-clock budget: if
 // the grid is not co-resident (or anything else goes wrong) all workgroups drain, the launch ends with ctl->abort set
 // and the host falls back to the launch chain (tests/test_gpu_parity.py exercises that path by sabotage).
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 #if defined(BRDF_STAMPS)
@@ -183,31 +177,6 @@ __device__ __forceinline__ void for_samples(int nk, F &&f) {
     for (int k = 0; k < nk; ++k) f(k);
   }
 }
-
-// two samples per guarded block where both exist: one sample's dependent chains (exp, the row differences, ten accumulations)
-// leave the fp64 pipe idle a third of the time with two waves per SIMD, two samples in one basic block let the scheduler
-// interleave them.  For the kernels whose register budget has the room (everything but the dlevmar_dif trial sweep).
-template <bool UNROLLED, class F>
-__device__ __forceinline__ void for_sample_pairs(int nk, F &&f) {
-  if constexpr (UNROLLED) {
-#pragma unroll
-    for (int k = 0; k < kRSpt; k += 2) {
-      if (k + 1 < nk) {
-        f(k);
-        f(k + 1);
-      } else if (k < nk) {
-        f(k);
-      }
-    }
-  } else {
-#pragma unroll 2
-    for (int k = 0; k < nk; ++k) f(k);
-  }
-}
-
-__device__ __forceinline__ constexpr bool pend_flag(std::true_type) { return true; }
-__device__ __forceinline__ constexpr bool pend_flag(std::false_type) { return false; }
-__device__ __forceinline__ constexpr bool pend_flag(bool b) { return b; }
 
 // Reduction of NS sums and one max over the eight waves: two DPP steps inside each row of 16 lanes leave the sum of
 // every 4 consecutive lanes in lanes 3,7,11,..; those park their values as buf[slot][thread/4]; wave w then owns slots
@@ -487,8 +456,7 @@ __device__ __forceinline__ void build_uniforms_wave(PassUniforms<MODEL> &u, cons
 // lane's partial sums in acc[] / mx and returns the number of sum slots of the request kind (a wave-uniform value).
 // `pend` (dlevmar_dif): the machine adopted the Broyden update of the previous trial; tb[] holds its scalar and
 // dpp[] its Dp: J += tb Dp^T is applied to the row while it is being read (lm_core.c:760-766).
-// PAIRS: two samples per guarded block in the evaluation / Jacobian sweeps (for_sample_pairs)
-template <int MODEL, int METHOD, bool FAST, bool PAIRS, class Store>
+template <int MODEL, int METHOD, bool FAST, class Store>
 __device__ __forceinline__ void sweep_pass(int kind, const PassUniforms<MODEL> &u, Store &st, double *jl, int tid, int nk, int nfull, unsigned okm,
                                            bool pend, const double *dpp, double *acc, double &mx) {
   constexpr bool U = Store::kUnrolled;
@@ -499,24 +467,13 @@ __device__ __forceinline__ void sweep_pass(int kind, const PassUniforms<MODEL> &
   // workgroup of a single fit holds up to #workgroups - 1 samples fewer than a tile, so its slot nk - 2 can be partly
   // empty and its slot nk - 1 entirely -- e.g. n = 262,145 on 256 CUs: tile 1025, last workgroup 770 samples.)
   auto dead = [&](int k) { return k >= nfull && !(okm >> k & 1u); };
-  // (measured, production builds, 10^6-sample Ward dlevmar_bc_dif with every candidate a Jacobian pass: 178 us per fit with
-  // pairs against 172 without -- the register-resident Jacobian body already interleaves its two exp chains; off by default)
-#ifdef BRDF_BC_PAIRS
-  constexpr bool kPairs = PAIRS;
-#else
-  constexpr bool kPairs = false;
-#endif
-  auto for_bc = [&](auto &&f) {
-    if constexpr (kPairs)
-      for_sample_pairs<U>(nk, f);
-    else
-      for_samples<U>(nk, f);
-  };
+  // (one sample per guarded block in the evaluation / Jacobian sweeps too.  Two were measured, 10^6-sample Ward dlevmar_bc_dif with every
+  // candidate a Jacobian pass: 178 against 172 us per fit -- the register-resident Jacobian body already interleaves its two exp chains)
   switch (kind) {
   case RQ_EVAL:  // (the four kinds only dlevmar_bc_dif / bc_der / der issue are compiled into those kernels only)
     if constexpr (METHOD != 0) {
       const EvalUniforms eu{scalar_copy(u.l0), scalar_copy(u.n0), 1.0};  // (scalar registers: see RQ_DIF_TRIAL)
-      for_bc([&](int k) {
+      for_samples<U>(nk, [&](int k) {
         const double f = model_value<MODEL, FAST>(eu, st.get(kFc0, k), prep(k));
         double e = st.get(kFx, k) - f;
         if (dead(k)) e = 0.0;
@@ -528,7 +485,7 @@ __device__ __forceinline__ void sweep_pass(int kind, const PassUniforms<MODEL> &
   case RQ_SCALED:
     if constexpr (METHOD != 0) {
       const EvalUniforms eu{scalar_copy(u.l0), scalar_copy(u.n0), scalar_copy(u.scal)};
-      for_bc([&](int k) {
+      for_samples<U>(nk, [&](int k) {
         const double f = model_value<MODEL, FAST>(eu, st.get(kFc0, k), prep(k));
         double t = (st.get(kFx, k) - f) / eu.scal;
         if (dead(k)) t = 0.0;
@@ -538,7 +495,6 @@ __device__ __forceinline__ void sweep_pass(int kind, const PassUniforms<MODEL> &
     break;
   case RQ_EVAL_MULTI:  // bc: candidates of a projected-gradient search; dif: the trial points of a chain of rejections
     if constexpr (METHOD != 2) {
-#ifndef BRDF_EXP_MULTI_GUARDED
       if (u.ncand == kMaxCand) {
         // the usual case, a full set of candidates: no `j < ncand` guard between the candidates of a sample, so that four
         // independent exp chains share a basic block and interleave (guarded, every candidate is a block of its own and its
@@ -590,7 +546,6 @@ __device__ __forceinline__ void sweep_pass(int kind, const PassUniforms<MODEL> &
         }
         break;
       }
-#endif
       for_samples<U>(nk, [&](int k) {
         const double c0 = st.get(kFc0, k), x = st.get(kFx, k);
         const Prep q = prep(k);
@@ -630,7 +585,7 @@ __device__ __forceinline__ void sweep_pass(int kind, const PassUniforms<MODEL> &
           ju.np2 = scalar_copy(u.np2);
           if (JK == 1) ju.nm2 = scalar_copy(u.nm2);
         }
-        for_bc([&](int k) {
+        for_samples<U>(nk, [&](int k) {
           double f0 = 0.0, j[kM];
           if (JK == 2)
             model_an_row<MODEL, FAST>(ju, st.get(kFc0, k), prep(k), f0, j);
@@ -644,26 +599,12 @@ __device__ __forceinline__ void sweep_pass(int kind, const PassUniforms<MODEL> &
           acc[kNL + kM] = fma(e, e, acc[kNL + kM]);
         });
       };
-#ifdef BRDF_EXP_OLD_JAC
-      for_bc([&](int k) {
-        double f0 = 0.0, j[kM];
-        if (u.analytic)
-          model_an_row<MODEL, FAST>(u, st.get(kFc0, k), prep(k), f0, j);
-        else
-          model_fd_row<MODEL, FAST>(u, st.get(kFc0, k), prep(k), true, f0, 0.0, false, j);
-        double e = st.get(kFx, k) - f0;
-        if (dead(k)) e = j[0] = j[1] = j[2] = 0.0;
-        acc_normal_eq_fma(j, e, acc, acc + kNL);
-        acc[kNL + kM] = fma(e, e, acc[kNL + kM]);
-      });
-#else
       if (u.analytic)
         jac(std::integral_constant<int, 2>{});
       else if (u.central)
         jac(std::integral_constant<int, 1>{});
       else
         jac(std::integral_constant<int, 0>{});
-#endif
     }
     break;
   case RQ_DIF_INIT:
@@ -695,7 +636,6 @@ __device__ __forceinline__ void sweep_pass(int kind, const PassUniforms<MODEL> &
     break;
   case RQ_DIF_TRIAL:  // speculative protocol: the Broyden-updated row is formed for the sums only (see the file comment)
     if constexpr (METHOD == 0) {
-#ifndef BRDF_EXP_LDS_UNIFORMS
       // The pass's uniforms live in LDS (the control wave builds them there); read through `su`, the sweep keeps them in VECTOR
       // registers, and every use of one in an fp64 instruction then costs a register, a copy or an operand slot.  Copied into
       // SCALAR registers once per sweep (readfirstlane: they are wave-uniform) the same loop runs 2.4x faster in isolation
@@ -714,14 +654,13 @@ __device__ __forceinline__ void sweep_pass(int kind, const PassUniforms<MODEL> &
       const double dpp_s[kM] = {scalar_copy(dpp[0]), scalar_copy(dpp[1]), scalar_copy(dpp[2])};
       const TrialUniforms &u = tu;  // (shadows the LDS uniforms for the rest of this case)
       const double *dpp = dpp_s;
-#endif
       const double rinv = 1.0 / u.dp_l2;
       auto value_q = [&](int k) { return model_value_q<MODEL, FAST>(u, st.get(kFc0, k), prep(k)); };
-      auto body = [&](auto pend_c, int k, const double w) {
+      auto body = [&](int k, const double w) {
         const int s = k * kRThreads + tid;
         const double h = st.get(kFhx, k), x = st.get(kFx, k);
         double jo[kM] = {jl[s], jl[kRCap + s], jl[2 * kRCap + s]};
-        if (pend_flag(pend_c)) {  // adopt the previous trial's update: the same operation that formed its jn[] below
+        if (pend) {  // adopt the previous trial's update: the same operation that formed its jn[] below
           const double tp = st.get(kFtb, k);
 #pragma unroll
           for (int j = 0; j < kM; ++j) jo[j] = fma(tp, dpp[j], jo[j]);
@@ -758,16 +697,7 @@ __device__ __forceinline__ void sweep_pass(int kind, const PassUniforms<MODEL> &
       };
       // (the exp chains of two samples side by side and the Broyden / accumulation halves one after the other was measured too:
       // 455 against 446 us per 10^6-sample fit; whole bodies in pairs spill 28-36 VGPRs)
-#ifdef BRDF_TRIAL_HOIST_PEND
-      // (whether the previous trial's update is pending is the same for every sample: chosen outside the body, which then is one
-      // basic block in which the exp chain, the LDS reads of the row and the Broyden arithmetic can interleave)
-      if (pend)
-        for_samples<U>(nk, [&](int k) { body(std::true_type{}, k, value_q(k)); });
-      else
-        for_samples<U>(nk, [&](int k) { body(std::false_type{}, k, value_q(k)); });
-#else
-      for_samples<U>(nk, [&](int k) { body(pend, k, value_q(k)); });  // (the branch stays in the body)
-#endif
+      for_samples<U>(nk, [&](int k) { body(k, value_q(k)); });  // (the `pend` branch stays in the body)
     }
     break;
   default: break;  // unknown request: the control wave will not survive it either
@@ -789,13 +719,8 @@ __device__ __forceinline__ void reduce_pass(int kind, const double *acc, double 
     switch (kind) {
     // (max |e| is read after plain evaluations only -- the overflow guards of lmbc_core.c:748, :915 -- so the Jacobian and
     // multi-candidate passes carry no max slot: one reduction value, one exchange cell and one gather instruction less)
-#ifdef BRDF_EXP_KEEP_MAX
-    case RQ_JAC: worker_reduce<SumLayout<kM>::JAC, true>(acc, mx, red, sums, st_, last_); break;
-    case RQ_EVAL_MULTI: worker_reduce<kMaxCand, true>(acc, mx, red, sums, st_, last_); break;
-#else
     case RQ_JAC: worker_reduce<SumLayout<kM>::JAC, false>(acc, mx, red, sums, st_, last_); break;
     case RQ_EVAL_MULTI: worker_reduce<kMaxCand, false>(acc, mx, red, sums, st_, last_); break;
-#endif
     default: worker_reduce<1, METHOD == 1>(acc, mx, red, sums, st_, last_); break;  // (dlevmar_der never reads max |e|)
     }
   }
@@ -962,20 +887,12 @@ __global__ __launch_bounds__(kRThreads) void resident_fit_kernel(ResidentCtx ctx
     // for the whole fit 11.29 against 10.53 in LDS -- although the step itself got shorter in the stamped build (6970 against
     // 7950 cycles: every `if (h.k < c.itmax ...)` in LDS is a dependent ds_read -> s_waitcnt -> compare -> branch); a register
     // copy made for every step (170 LDS operations to copy in and out) and all of the machine in registers (105 VGPRs
-    // spilled) were slower still.  -DBRDF_CORE_IN_REGS builds the first variant (never for dlevmar_bc_dif: its machine --
-    // line search, 8 projected-gradient candidates -- spills 160 VGPRs next to its own step code).
-#ifdef BRDF_CORE_IN_REGS
-    constexpr bool kCoreInRegs = METHOD != 1;
-#else
-    constexpr bool kCoreInRegs = false;
-#endif
-    typename Machine::Core hcore = sm.h;
-    if constexpr (kCoreInRegs) Machine::uniform_ints(hcore);
+    // spilled) were slower still.
     // dlevmar_dif: what the step reads in every pass but never (constants: options, limits) or only itself (its counters and
     // flags) changes lives in SCALAR registers for the whole fit; the reals stay in LDS with the rest of the machine.  On an
     // LDS-resident machine every `if (h.k < c.itmax ...)` is a dependent ds_read -> s_waitcnt -> compare -> branch.  Same box,
     // 10^6-sample fits: Ward 403.2 -> 401.9 us (constants) -> 398.8 us (+ counters), Blinn-Phong 342.9 -> 338.2 us; all of
-    // Machine::Core in (vector) registers was slower (BRDF_CORE_IN_REGS above), the integers alone cost no vector register.
+    // Machine::Core in (vector) registers was slower (see above), the integers alone cost no vector register.
     typename Machine::Cold cold0;
     typename std::conditional<METHOD == 0, typename DifMachine<kM>::CoreInts, int>::type ints_regs{};
     if constexpr (METHOD == 0) {
@@ -1011,32 +928,15 @@ __global__ __launch_bounds__(kRThreads) void resident_fit_kernel(ResidentCtx ctx
         double mx = 0.0;
         const double dpp[kM] = {dp_prev[0], dp_prev[1], dp_prev[2]};
         if constexpr (kControlFromLds) {
-#ifndef BRDF_EXP_CONTROL_REGS
           decisions(ls, pend);
-          sweep_pass<MODEL, METHOD, FAST, !BATCHED>(kind, su, ls, jl, tid, nk, nfull, okm, pend, dpp, acc, mx);
-#else
-          // (measured and lost, -DBRDF_EXP_CONTROL_REGS: the parked samples brought into registers for the sweep by one burst of ds_reads,
+          sweep_pass<MODEL, METHOD, FAST>(kind, su, ls, jl, tid, nk, nfull, okm, pend, dpp, acc, mx);
+          // (measured and lost: the parked samples brought into registers for the sweep by one burst of ds_reads,
           // the other waves' unrolled register sweep, what the pass changed parked again.  The rolled LDS loop below pays the LDS latency
           // of a sample's seven fields -- 7.0k ticks per sweep against the register waves' ~5k -- but the burst variant spills 46 VGPRs
           // inside the sweep: 480 against 425 us per 10^6-sample fit.)
-#pragma unroll
-          for (int f = 0; f < NF; ++f)
-#pragma unroll
-            for (int k = 0; k < kRSpt; ++k) rs.v[f][k] = ls.get(f, k);
-          decisions(rs, pend);
-          sweep_pass<MODEL, METHOD, FAST, !BATCHED>(kind, su, rs, jl, tid, nk, nfull, okm, pend, dpp, acc, mx);
-          if constexpr (METHOD == 0) {
-#pragma unroll
-            for (int k = 0; k < kRSpt; ++k) {
-              ls.set(kFhx, k, rs.v[kFhx][k]);
-              ls.set(kFwrk, k, rs.v[kFwrk][k]);
-              ls.set(kFtb, k, rs.v[kFtb][k]);
-            }
-          }
-#endif
         } else {
           decisions(rs, pend);
-          sweep_pass<MODEL, METHOD, FAST, !BATCHED>(kind, su, rs, jl, tid, nk, nfull, okm, pend, dpp, acc, mx);
+          sweep_pass<MODEL, METHOD, FAST>(kind, su, rs, jl, tid, nk, nfull, okm, pend, dpp, acc, mx);
         }
         RSTAMP(5);  // the control wave's own sweep
         RTRACE(ctx, epoch, 1, wall_clock64());
@@ -1080,23 +980,13 @@ __global__ __launch_bounds__(kRThreads) void resident_fit_kernel(ResidentCtx ctx
       }
       if (kind == RQ_DIF_TRIAL) {
         if constexpr (METHOD == 0) {
-          if constexpr (kCoreInRegs)
-            expand_trial_sums(hcore, sm.h.cool, su.dp, sums);
-          else
-            expand_trial_sums(static_cast<const typename Machine::Core &>(sm.h), sm.h.cool, su.dp, sums);
+          expand_trial_sums(static_cast<const typename Machine::Core &>(sm.h), sm.h.cool, su.dp, sums);
         }
 #pragma unroll
         for (int j = 0; j < kM; ++j) dp_prev[j] = su.dp[j];
         dp_prev[kM] = su.dp_l2;
       }
-      // The LM step.  kCoreInRegs: the machine's busy half (Machine::Core) lives in this wave's REGISTERS for the whole fit
-      // (hcore, loaded before the loop); Cool and the request stay in LDS, where the other waves read the request.
-      if constexpr (kCoreInRegs) {
-        if constexpr (METHOD == 0)
-          Machine::template run<true, true>(sm.c, hcore, sm.h.cool, sm.h.req, sums, sums[kSums]);
-        else
-          Machine::template run<true>(sm.c, hcore, sm.h.req, sums, sums[kSums]);
-      } else {
+      {  // the LM step, on the machine in LDS
         if constexpr (METHOD == 0) {  // (+ chains of rejections, several trial points to a sweep)
           typename Machine::Cold cc;  // (results are written by the finishing step only and stored right behind it: nothing carried)
           cc.itmax = cold0.itmax, cc.n = cold0.n, cc.want_covar = cold0.want_covar, cc.refresh = cold0.refresh;
@@ -1132,7 +1022,6 @@ __global__ __launch_bounds__(kRThreads) void resident_fit_kernel(ResidentCtx ctx
       __syncthreads();  // B: the next request and its uniforms are in LDS
       RSTAMP(4);
     }
-    if constexpr (kCoreInRegs) static_cast<typename Machine::Core &>(sm.h) = hcore;
     if constexpr (BATCHED) {
       if (tid == 0) {
         double *po = bctx.p + (size_t)fit * kM;
@@ -1181,7 +1070,7 @@ __global__ __launch_bounds__(kRThreads) void resident_fit_kernel(ResidentCtx ctx
     for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
     double mx = 0.0;
     const double dpp[kM] = {dp_prev[0], dp_prev[1], dp_prev[2]};
-    sweep_pass<MODEL, METHOD, FAST, !BATCHED>(kind, su, rs, jl, tid, nk, nfull, okm, pend, dpp, acc, mx);
+    sweep_pass<MODEL, METHOD, FAST>(kind, su, rs, jl, tid, nk, nfull, okm, pend, dpp, acc, mx);
 #ifdef BRDF_TRACE_WORKERS  // (diagnostic: when do the register-resident waves finish their sweeps? slots 6, 7 = waves 4, 7)
     if constexpr (!BATCHED) {
       if (wave == 4) RTRACE(ctx, wepoch, 6, wall_clock64());
@@ -1196,249 +1085,42 @@ __global__ __launch_bounds__(kRThreads) void resident_fit_kernel(ResidentCtx ctx
 }
 
 // ---------------------------------------------------------------------------------------------------
-// host side
+// what an instance exports: a host function that tells its kernels' addresses (the host side that launches them is resident_fit.hip)
 // ---------------------------------------------------------------------------------------------------
-#define HIP_OK(call)                                                                  \
-  do {                                                                                \
-    hipError_t e_ = (call);                                                           \
-    if (e_ != hipSuccess) {                                                           \
-      set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return kLmError;                                                                \
-    }                                                                                 \
-  } while (0)
-
-struct RWorkspace {
-  int device = -1, cus = 0;
-  char *d_block = nullptr;  // ctl | machine | rows[2][kRowWords][kRowStride]
-  Mailbox *h_mbox = nullptr, *d_mbox = nullptr;
-  static constexpr size_t kMachineBytes = 4096;
-  static constexpr size_t off_machine = sizeof(ResidentCtl);
-  static constexpr size_t off_rows = off_machine + kMachineBytes;
-  static constexpr size_t rows_bytes = sizeof(u64) * (kRowsGranules + kGroupsGranules);  // rows + group rows
-  static constexpr size_t trace_bytes = sizeof(long long) * 8 * kRowStride;
-  long long h_trace[8 * (kRowStride + 1)] = {0};  // + one row: the sections of the LM step (LM_STAMP)
-  unsigned tag_base = 0;
-  FitStats stats{};
-  LaunchTimer timer;
-  // After a launch that could not run co-resident (GPU shared with other kernels / ranks: every workgroup burns its
-  // spin budget before the launch drains) the resident path steps aside for the next `skip` fits, doubling up to
-  // 1024 while it keeps failing, instead of paying that budget on every fit.
-  int backoff = 0, skip = 0;
-
-  // the blocks belong to `device`: drain and free them THERE, whatever device is current now
-  void release() {
-    if (!d_block && !h_mbox) return;
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    if (device >= 0 && cur != device) (void)hipSetDevice(device);
-    (void)hipDeviceSynchronize();
-    if (d_block) (void)hipFree(d_block);
-    if (h_mbox) (void)hipHostFree(h_mbox);
-    if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
-    d_block = nullptr;
-    h_mbox = d_mbox = nullptr;
-  }
-  ~RWorkspace() { release(); }
-  int ensure(int dev) {
-    if (device == dev && d_block) return 0;
-    release();
-    device = dev;
-    hipDeviceProp_t prop;
-    HIP_OK(hipGetDeviceProperties(&prop, dev));
-    cus = prop.multiProcessorCount;
-    HIP_OK(hipMalloc(&d_block, off_rows + rows_bytes + trace_bytes));
-    HIP_OK(hipMemset(d_block, 0, off_rows + rows_bytes + trace_bytes));
-    tag_base = 0;
-    HIP_OK(hipHostMalloc(&h_mbox, sizeof(Mailbox), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_OK(hipHostGetDevicePointer((void **)&d_mbox, h_mbox, 0));
-    return 0;
-  }
+using ResidentKernelFn = void (*)(ResidentCtx, BatchCtx);
+constexpr int kFastPath = 0, kExactPath = 1;
+struct ResidentKernels {
+  ResidentKernelFn single[2], batched[2];  // [kFastPath], [kExactPath] (null for Ward, which has no exact path)
+#ifdef BRDF_STAMPS
+  void (*take_lm_stamps)(long long *out8);  // the instance's g_rlm_stamps -> out8, and zeroed
+#endif
 };
-template <int MODEL, int METHOD, bool FAST>
-int resident_attempt(const StreamFitArgs &a, RWorkspace &ws, bool *retry_exact, bool *unavailable) {
-  using Machine = RMachine<METHOD>;
-  static_assert(sizeof(Machine) <= 4096, "resident workspace layout");
-  *retry_exact = *unavailable = false;
-  const int G = (int)std::min<long long>(ws.cus, std::max<long long>(1, ((long long)a.n + 1023) / 1024));
-  Machine m;  // started here for the entry point's argument checks and warnings only: the kernel starts its own
-  memset(&m, 0, sizeof m);
-  if constexpr (METHOD == 0) {
-    m.start(a.p, a.n, a.itmax, a.opts, a.covar != nullptr, /*speculative=*/1);
-    if (m.h.req.kind == RQ_DONE) {
-      set_error("dlevmar_dif(): cannot solve a problem with fewer measurements [%d] than unknowns [%d]", a.n, kM);
-      return kLmError;
-    }
-  } else if constexpr (METHOD == 2) {
-    m.start(a.p, a.n, a.itmax, a.opts, a.covar != nullptr);
-    if (m.h.req.kind == RQ_DONE) {
-      set_error("dlevmar_der(): cannot solve a problem with fewer measurements [%d] than unknowns [%d]", a.n, kM);
-      return kLmError;
-    }
-  } else {
-    m.start(a.p, a.n, a.lb, a.ub, a.dscl, a.itmax, a.opts, a.covar != nullptr, pg_candidates());
-    m.c.analytic_jac = a.analytic ? 1 : 0;
-    if (m.h.req.kind == RQ_DONE) {
-      switch (m.c.bad_input) {
-      case 1: set_error("dlevmar_bc_dif(): cannot solve a problem with fewer measurements [%d] than unknowns [%d]", a.n, kM); break;
-      case 2: set_error("dlevmar_bc_dif(): at least one lower bound exceeds the upper one"); break;
-      default: set_error("dlevmar_bc_dif(): scaling constants should be positive"); break;
-      }
-      return kLmError;
-    }
-    if (FAST || !brdf_fast_path_enabled())  // (an exact re-run must not print the warning twice)
-      for (int i = 0; i < kM; ++i)          // same warning as lmbc_core.c:516-520
-        if (m.c.infeasible_mask & (1 << i))
-          fprintf(stderr, "Warning: component %d of starting point not feasible in dlevmar_bc_dif()! [%g projected to %g]\n",
-                  i, m.c.p_start[i], m.h.p[i]);
-  }
-  Mailbox &mb = *ws.h_mbox;
-  memset(&mb, 0, sizeof mb);
-  if (ws.tag_base > 0xF0000000u) {  // tag space nearly used up: start over from zeroed rows (and control words)
-    HIP_OK(hipMemsetAsync(ws.d_block, 0, RWorkspace::off_rows + RWorkspace::rows_bytes, a.stream));
-    ws.tag_base = 0;
-  }
 
-  ResidentCtx c;
-  c.c0 = a.d_angles;
-  c.c1 = a.d_angles + a.n;
-  c.c2 = a.d_angles + 2 * (size_t)a.n;
-  c.x = a.d_x;
-  c.ctl = reinterpret_cast<ResidentCtl *>(ws.d_block);
-  c.rows = reinterpret_cast<u64 *>(ws.d_block + RWorkspace::off_rows);
-  c.groups = c.rows + kRowsGranules;
-  c.launch_id = ws.tag_base + 1u;  // (tag_base grows by passes + 2 with every launch)
-  for (int i = 0; i < kM; ++i) {
-    c.p0[i] = a.p[i];
-    c.lb[i] = a.lb ? a.lb[i] : 0.0;
-    c.ub[i] = a.ub ? a.ub[i] : 0.0;
-    c.dscl[i] = a.dscl ? a.dscl[i] : 1.0;
-  }
-  for (int i = 0; i < 5; ++i) c.opts[i] = a.opts ? a.opts[i] : 0.0;
-  c.itmax = a.itmax;
-  c.has_opts = a.opts != nullptr;
-  c.has_lb = METHOD == 1 && a.lb != nullptr;
-  c.has_ub = METHOD == 1 && a.ub != nullptr;
-  c.has_dscl = METHOD == 1 && a.dscl != nullptr;
-  c.want_covar = a.covar != nullptr;
-  c.multi = pg_candidates();
-  c.chain = dif_chain_candidates();
-  c.spec_jac = bc_spec_jac_enabled() ? 1 : 0;
-  c.analytic = a.analytic ? 1 : 0;
-  c.mbox = ws.d_mbox;
-  c.n = a.n;
-  c.tag_base = ws.tag_base;
-  c.spin_ticks = kSpinBudgetTicks;
-  c.sabotage_epoch = -1;
-  c.replicas = kReplicas;
-  c.trace = nullptr;
-  c.trace_epoch = -1;
-#ifdef BRDF_STAMPS
-  c.trace = reinterpret_cast<long long *>(ws.d_block + RWorkspace::off_rows + RWorkspace::rows_bytes);
-  c.trace_epoch = 20;
-  if (const char *e = getenv("BRDF_HIP_RESIDENT_TRACE_EPOCH")) c.trace_epoch = atoi(e);
-#endif
-  if (const char *e = getenv("BRDF_HIP_RESIDENT_REPLICAS")) c.replicas = std::min(kReplicas, std::max(1, atoi(e)));
-  if (const char *e = getenv("BRDF_HIP_RESIDENT_SPIN_MS")) c.spin_ticks = std::max(1LL, atoll(e)) * 100000LL;
-  if (const char *e = getenv("BRDF_HIP_RESIDENT_SABOTAGE")) c.sabotage_epoch = atoi(e);  // tests only: forces the fallback
-
-  {  // one workgroup per CU must be able to live there at all (registers, LDS): checked once per kernel (atomic: host
-     // threads on several devices may get here at once)
-    static std::atomic<int> per_cu_once{-1};
-    int per_cu = per_cu_once.load(std::memory_order_relaxed);
-    if (per_cu < 0) {
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resident_fit_kernel<MODEL, METHOD, FAST, false>, kRThreads, 0) != hipSuccess)
-        per_cu = 0;
-      per_cu_once.store(per_cu, std::memory_order_relaxed);
-    }
-    if (per_cu < 1) {
-      *unavailable = true;
-      return 0;
-    }
-  }
-  ws.timer.before(a.stream);
-  hipLaunchKernelGGL((resident_fit_kernel<MODEL, METHOD, FAST, false>), dim3(G), dim3(kRThreads), 0, a.stream, c, BatchCtx{});
-  HIP_OK(hipGetLastError());
-  ws.timer.after(a.stream);
-  {  // wait on the pinned mailbox (a stream synchronise sleeps and wakes up tens of microseconds late); the launch
-     // always terminates (bounded spins), which hipStreamQuery reports even if `done` never comes
-    volatile int *done = &mb.done;
-    for (unsigned spins = 0; !*done; ++spins)
-      if ((spins & 0x3FFu) == 0x3FFu && hipStreamQuery(a.stream) != hipErrorNotReady) break;
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  }
-  if (!mb.done) {
-    HIP_OK(hipStreamSynchronize(a.stream));
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  }
-  if (!mb.done) {  // aborted: not co-resident / spin budget exhausted.  Tags of unknown epochs were stored: start over
-    (void)hipMemsetAsync(ws.d_block, 0, RWorkspace::off_rows + RWorkspace::rows_bytes, a.stream);
-    ws.tag_base = 0;
-    *unavailable = true;
-    return 0;
-  }
-  ws.tag_base += (unsigned)mb.passes + 2u;
-#ifdef BRDF_STAMPS
-  (void)hipMemcpy(ws.h_trace, c.trace, RWorkspace::trace_bytes, hipMemcpyDeviceToHost);
-  (void)hipMemcpyFromSymbol(ws.h_trace + 8 * kRowStride, HIP_SYMBOL(g_rlm_stamps), sizeof(long long) * 8);
-  {
-    long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_rlm_stamps), zero, sizeof zero);
-  }
-#endif
-  if (FAST && mb.domain_bad) {
-    *retry_exact = true;
-    return 0;
-  }
-  for (int i = 0; i < kM; ++i) a.p[i] = mb.p[i];
-  if (a.info)
-    for (int i = 0; i < kInfoSz; ++i) a.info[i] = mb.info[i];
-  if (a.covar)
-    for (int i = 0; i < kM * kM; ++i) a.covar[i] = mb.covar[i];
-  ws.stats.passes = mb.passes;
-  ws.stats.launches = 1;
-  ws.stats.jac_passes = mb.n_jac;
-  ws.stats.eval_passes = mb.n_eval;
-  ws.stats.device_us = (double)(mb.t_last - mb.t_first) / 100.0;  // first pass start -> result (s_memrealtime, 100 MHz)
-  ws.stats.kernel_us = ws.timer.elapsed_us();
-  for (int k = 0; k < 8; ++k) ws.stats.stamps[k] = mb.stamps[k];
-  return mb.ret;
-}
-
-template <int MODEL, int METHOD>
-int resident_run_mm(const StreamFitArgs &a, RWorkspace &ws, bool *unavailable) {
-  bool retry = false;
-  double keep[kM];
-  for (int i = 0; i < kM; ++i) keep[i] = a.p[i];
-  int ret;
-  if (brdf_fast_path_enabled() || MODEL == MODEL_WARD) {
-    ret = resident_attempt<MODEL, METHOD, true>(a, ws, &retry, unavailable);
-    if (!retry || *unavailable) return ret;
-    for (int i = 0; i < kM; ++i) a.p[i] = keep[i];
-  }
-  if constexpr (MODEL != MODEL_WARD)
-    return resident_attempt<MODEL, METHOD, false>(a, ws, &retry, unavailable);
+// a kernel's address; null for Ward's exact path (taking the address would instantiate a kernel that is not built)
+template <int MODEL, int METHOD, bool FAST, bool BATCHED>
+constexpr ResidentKernelFn resident_kernel() {
+  if constexpr (FAST || MODEL != MODEL_WARD)
+    return resident_fit_kernel<MODEL, METHOD, FAST, BATCHED>;
   else
-    return kLmError;
+    return nullptr;
 }
 
-template <int MODEL, int METHOD>
-int resident_batch_mm(bool fast, const BatchCtx &c, hipStream_t stream) {
-  const dim3 grid(c.S), block(kRThreads);
-  const ResidentCtx none{};
-  if (fast) {
-    hipLaunchKernelGGL((resident_fit_kernel<MODEL, METHOD, true, true>), grid, block, 0, stream, none, c);
-    HIP_OK(hipGetLastError());
-  }
-  if constexpr (MODEL != MODEL_WARD) {  // fits with a cosine <= 0 marked themselves (or all are marked: exact mode)
-    hipLaunchKernelGGL((resident_fit_kernel<MODEL, METHOD, false, true>), grid, block, 0, stream, none, c);
-    HIP_OK(hipGetLastError());
-  }
-  return 0;
+#ifdef BRDF_STAMPS
+static void take_lm_stamps(long long *out8) {
+  const long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_rlm_stamps), sizeof zero);
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_rlm_stamps), zero, sizeof zero);
 }
+#define BRDF_RESIDENT_STAMPS_ENTRY , take_lm_stamps
+#else
+#define BRDF_RESIDENT_STAMPS_ENTRY
+#endif
 
-// one translation unit per (MODEL, METHOD): resident_inst.hip defines these two entry points for its pair
-#define BRDF_RESIDENT_INSTANCE(MODEL_, METHOD_, NAME_)                                                                        \
-  int resident_run_##NAME_(const StreamFitArgs &a, RWorkspace &ws, bool *unavailable) { return resident_run_mm<MODEL_, METHOD_>(a, ws, unavailable); } \
-  int resident_batch_##NAME_(bool fast, const BatchCtx &c, hipStream_t stream) { return resident_batch_mm<MODEL_, METHOD_>(fast, c, stream); }
+// one translation unit per (MODEL, METHOD): resident_inst.hip defines this function for its pair
+#define BRDF_RESIDENT_INSTANCE(MODEL_, METHOD_, NAME_)                                                                      \
+  ResidentKernels resident_kernels_##NAME_() {                                                                              \
+    return {{resident_kernel<MODEL_, METHOD_, true, false>(), resident_kernel<MODEL_, METHOD_, false, false>()},            \
+            {resident_kernel<MODEL_, METHOD_, true, true>(), resident_kernel<MODEL_, METHOD_, false, true>()} BRDF_RESIDENT_STAMPS_ENTRY}; \
+  }
 
 }  // namespace brdf

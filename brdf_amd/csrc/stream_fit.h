@@ -87,7 +87,7 @@ FitStats stream_fit_last_stats();
 // roofline reads it; off by default: two event records and one event wait per fit)
 bool launch_timing_enabled();
 void set_launch_timing(bool on);
-// an event pair per host thread, created on first use (resident_fit_impl.h / channels_fit_impl.h)
+// an event pair per host thread, created on first use (fit_host.h: ResidentWorkspace)
 struct LaunchTimer {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int device = -1;  // the events belong to the device they were created on

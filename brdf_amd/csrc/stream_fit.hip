@@ -27,7 +27,7 @@ __device__ long long g_lm_last;
 #if defined(BRDF_STAMPS) && defined(__HIP_DEVICE_COMPILE__)
 #define LM_STAMP(i) do { if (blockIdx.x == 0) { const long long now_ = clock64(); if ((i) != 0) g_lm_stamps[i] += now_ - g_lm_last; g_lm_last = now_; } } while (0)
 #endif
-#include "stream_fit.h"
+#include "fit_host.h"
 
 namespace brdf {
 
@@ -459,15 +459,6 @@ void set_error(const char *fmt, ...) {
 }
 const char *get_error() { return g_err; }
 
-#define HIP_OK(call)                                                                  \
-  do {                                                                                \
-    hipError_t e_ = (call);                                                           \
-    if (e_ != hipSuccess) {                                                           \
-      set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return kLmError;                                                                \
-    }                                                                                 \
-  } while (0)
-
 namespace {
 
 struct Workspace {
@@ -556,8 +547,6 @@ int blocks_for(int n) {
 
 static thread_local bool g_last_was_resident = false;
 FitStats stream_fit_last_stats() { return g_last_was_resident ? resident_fit_last_stats() : g_ws.stats; }
-bool brdf_fast_path_enabled();
-int pg_candidates();
 
 // one attempt on the FAST (prepared-sample) or the exact model path; *retry_exact is set when the FAST path
 // met a cosine <= 0 and the result must be discarded
@@ -585,38 +574,8 @@ static int stream_fit_attempt(const StreamFitArgs &a, bool fast, bool *retry_exa
   h.jac[0] = ws.d_dif + 2 * (size_t)a.n;
   h.jac[1] = ws.d_dif + 5 * (size_t)a.n;
 
-  if (a.method == 0) {
-    DifMachine<kM> &m = h.m[0].dif;
-    m.start(a.p, a.n, a.itmax, a.opts, a.covar != nullptr, /*speculative=*/1, dif_chain_candidates());
-    if (m.h.req.kind == RQ_DONE) {
-      set_error("dlevmar_dif(): cannot solve a problem with fewer measurements [%d] than unknowns [%d]", a.n, kM);
-      return kLmError;
-    }
-  } else if (a.method == 2) {
-    DerMachine<kM> &m = h.m[0].der;
-    m.start(a.p, a.n, a.itmax, a.opts, a.covar != nullptr);
-    if (m.h.req.kind == RQ_DONE) {
-      set_error("dlevmar_der(): cannot solve a problem with fewer measurements [%d] than unknowns [%d]", a.n, kM);
-      return kLmError;
-    }
-  } else {
-    BcMachine<kM> &m = h.m[0].bc;
-    m.start(a.p, a.n, a.lb, a.ub, a.dscl, a.itmax, a.opts, a.covar != nullptr, pg_candidates(), bc_spec_jac_enabled() ? 1 : 0);
-    m.c.analytic_jac = a.analytic ? 1 : 0;
-    if (m.h.req.kind == RQ_DONE) {
-      switch (m.c.bad_input) {
-      case 1: set_error("dlevmar_bc_dif(): cannot solve a problem with fewer measurements [%d] than unknowns [%d]", a.n, kM); break;
-      case 2: set_error("dlevmar_bc_dif(): at least one lower bound exceeds the upper one"); break;
-      default: set_error("dlevmar_bc_dif(): scaling constants should be positive"); break;
-      }
-      return kLmError;
-    }
-    if (fast || !brdf_fast_path_enabled())  // (an exact re-run must not print the warning twice)
-      for (int i = 0; i < kM; ++i)          // same warning as lmbc_core.c:516-520
-        if (m.c.infeasible_mask & (1 << i))
-          fprintf(stderr, "Warning: component %d of starting point not feasible in dlevmar_bc_dif()! [%g projected to %g]\n",
-                  i, m.c.p_start[i], m.h.p[i]);
-  }
+  if (start_fit_machine(h.m[0], a.method, a.p, a.n, a.lb, a.ub, a.dscl, a.itmax, a.opts, a.covar != nullptr, a.analytic != 0, fast) != 0)
+    return kLmError;  // (h.m[0]: the machine the launches start from)
 
   Mailbox &mb = *ws.h_mbox;
   memset(&mb, 0, sizeof mb);
@@ -657,18 +616,9 @@ static int stream_fit_attempt(const StreamFitArgs &a, bool fast, bool *retry_exa
     return 0;
   }
 
-  for (int i = 0; i < kM; ++i) a.p[i] = mb.p[i];
-  if (a.info)
-    for (int i = 0; i < kInfoSz; ++i) a.info[i] = mb.info[i];
-  if (a.covar)
-    for (int i = 0; i < kM * kM; ++i) a.covar[i] = mb.covar[i];
-  ws.stats.passes = mb.passes;
+  mailbox_to_caller(mb, a.p, a.info, a.covar, &ws.stats);
   ws.stats.launches = pass;
-  ws.stats.jac_passes = mb.n_jac;
-  ws.stats.eval_passes = mb.n_eval;
-  ws.stats.device_us = (double)(mb.t_last - mb.t_first) / 100.0;  // s_memrealtime ticks at 100 MHz
   ws.stats.kernel_us = -1.0;  // (a chain of launches with host decisions in between: timed by its callers' events)
-  for (int k = 0; k < 8; ++k) ws.stats.stamps[k] = mb.stamps[k];
 #ifdef BRDF_STAMPS
   if (const char *path = getenv("BRDF_HIP_STEP_DUMP")) {  // diagnostic: per-pass cost of the LM step by transition
     static StreamCtx tmp;

@@ -333,6 +333,16 @@ def test_channels_sharing_a_launch_equal_single_fits_bit_for_bit(gpu, model, n):
         for c in range(K):
             alone = brdf_amd.fit_single(method, model, a, xd[c], synth.P0[model], itmax=synth.ITMAX, opts=synth.OPTS)
             assert np.array_equal(res[c].p, alone.p) and np.array_equal(res[c].info, alone.info)
+    # four channels (the fourth: channel 1's measurements again, not channel 0's): every channel's statistics are its own
+    kw = dict(lb=synth.LB, ub=synth.UB, itmax=synth.ITMAX, opts=synth.OPTS)
+    res = brdf_amd.fit_channels(1, model, a, torch.cat([xd, xd[1:2]]), synth.P0[model], **kw)
+    st = brdf_amd.last_channels_stats(4)
+    assert not st["shared_launch"]
+    for c in range(4):
+        alone = brdf_amd.fit_single(1, model, a, xd[c if c < 3 else 1], synth.P0[model], **kw)
+        assert np.array_equal(res[c].p, alone.p) and np.array_equal(res[c].info, alone.info), c
+        if c == 0:
+            assert st["channels"][0]["passes"] == brdf_amd.last_fit_stats()["passes"]
 
 
 def test_channel_launch_drains_when_a_workgroup_never_arrives(gpu, monkeypatch):
