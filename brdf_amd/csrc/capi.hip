@@ -16,6 +16,7 @@
 #include "../../include/brdf_levmar.h"
 #include "batch_fit.h"
 #include "fit_host.h"
+#include "fit_stats.h"
 
 namespace brdf {
 int generic_fit_run(int method, void (*func)(double *, double *, int, int, void *),
@@ -604,6 +605,71 @@ int brdf_hip_fit_batch(int method, int model, const double *angles, const double
   return bad;
 }
 
+int brdf_hip_fit_stats_batch_dev(int method, int model, const double *d_angles, const double *d_x, int S, int n,
+                                 const double *d_p, const double *opts, double *d_covar, double *d_stats, int *d_rank,
+                                 void *stream) {
+  FitStatsArgs a;
+  a.method = method;
+  a.model = model;
+  a.d_angles = d_angles;
+  a.d_x = d_x;
+  a.S = S;
+  a.n = n;
+  a.d_p = d_p;
+  a.opts = opts;
+  a.d_covar = d_covar;
+  a.d_stats = d_stats;
+  a.d_rank = d_rank;
+  a.stream = static_cast<hipStream_t>(stream);
+  return fit_stats_enqueue(a, "brdf_hip_fit_stats_batch_dev");
+}
+
+int brdf_hip_fit_stats_batch(int method, int model, const double *angles, const double *x, int S, int n, const double *p,
+                             const double *opts, double *covar, double *stats, int *rank) {
+  static const char *who = "brdf_hip_fit_stats_batch";
+  FitStatsArgs a;
+  a.method = method;
+  a.model = model;
+  a.d_angles = angles;  // (host pointers: checked for null only)
+  a.d_x = x;
+  a.S = S;
+  a.n = n;
+  a.d_p = p;
+  a.opts = opts;
+  a.d_covar = covar;
+  a.d_stats = stats;
+  a.d_rank = rank;
+  if (fit_stats_check(a, who) != 0) return LM_ERROR;
+  const size_t sn = (size_t)S * n;
+  DevBuf d_angles, d_x, d_p, d_covar, d_stats, d_rank;
+  if (d_angles.alloc(3 * sn) || d_x.alloc(sn) || d_p.alloc(3 * (size_t)S) || (covar && d_covar.alloc(9 * (size_t)S)) ||
+      (stats && d_stats.alloc(BRDF_STATS_SZ * (size_t)S)) || (rank && d_rank.alloc(((size_t)S + 1) / 2 + 1)))
+    return LM_ERROR;
+  hipError_t e = hipMemcpy(d_angles.ptr, angles, sizeof(double) * 3 * sn, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_x.ptr, x, sizeof(double) * sn, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_p.ptr, p, sizeof(double) * 3 * S, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    set_error("%s(): host->device copy failed: %s", who, hipGetErrorString(e));
+    return LM_ERROR;
+  }
+  a.d_angles = d_angles.ptr;
+  a.d_x = d_x.ptr;
+  a.d_p = d_p.ptr;
+  a.d_covar = d_covar.ptr;
+  a.d_stats = d_stats.ptr;
+  a.d_rank = reinterpret_cast<int *>(d_rank.ptr);
+  if (fit_stats_enqueue(a, who) != 0) return LM_ERROR;
+  e = hipStreamSynchronize(nullptr);
+  if (e == hipSuccess && covar) e = hipMemcpy(covar, d_covar.ptr, sizeof(double) * 9 * S, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && stats) e = hipMemcpy(stats, d_stats.ptr, sizeof(double) * BRDF_STATS_SZ * S, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && rank) e = hipMemcpy(rank, d_rank.ptr, sizeof(int) * S, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    set_error("%s(): %s", who, hipGetErrorString(e));
+    return LM_ERROR;
+  }
+  return 0;
+}
+
 int brdf_hip_model_eval_dev(int model, const double *d_angles, int n, const double *p, double *d_hx, void *stream) {
   return model_eval_run(model, d_angles, n, p, d_hx, static_cast<hipStream_t>(stream));
 }
@@ -629,6 +695,17 @@ int brdf_hip_fit_capture_dev(int model, const unsigned char *d_images, int L, in
                              long long *n_pixels, void *stream) {
   return capture_fit_run(model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin,
                          rv_mode, p0, lb, ub, itmax, opts, d_brdf_surfaces, avg, n_pixels, static_cast<hipStream_t>(stream));
+}
+
+int brdf_hip_fit_capture_stats_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                   const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf,
+                                   const double *leds, const double *view_origin, int rv_mode, const double *p0,
+                                   const double *lb, const double *ub, int itmax, const double *opts, double *d_brdf_surfaces,
+                                   double *avg, long long *n_pixels, void *stream, double *d_surface_covar,
+                                   double *d_surface_stats, int *d_surface_rank) {
+  return capture_fit_run(model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin,
+                         rv_mode, p0, lb, ub, itmax, opts, d_brdf_surfaces, avg, n_pixels, static_cast<hipStream_t>(stream),
+                         d_surface_covar, d_surface_stats, d_surface_rank);
 }
 
 int brdf_hip_fit_capture_single_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,

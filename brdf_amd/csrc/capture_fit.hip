@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "batch_fit.h"
+#include "fit_stats.h"
 #include "stream_fit.h"
 
 namespace brdf {
@@ -115,6 +116,16 @@ __global__ __launch_bounds__(kCT) void store_kernel(const double *p, const int *
   if (threadIdx.x < 3) block_sums[(size_t)blockIdx.x * 3 + threadIdx.x] = red[threadIdx.x][0];
 }
 
+// the optional statistics tail: row (face, channel) of the three maps reads the fit store_kernel's rule picks for it -- channel c
+// of the face's LAST pixel -- or nothing (-1) where no pixel carries the face
+__global__ __launch_bounds__(kCT) void stats_rows_kernel(const long long *last_of_face, int nf, int *src_of_row) {
+  const int r = blockIdx.x * kCT + threadIdx.x;
+  if (r >= 3 * nf) return;
+  const int f = r / 3;
+  const long long last = last_of_face[f];
+  src_of_row[r] = last ? (int)(3 * (last - 1) + (r - 3 * f)) : -1;
+}
+
 // ---- single-BRDF variant (CalcBRDFEquation_SingleBRDF, brdfdata.cpp:1138-1186) --------------------------------
 __global__ __launch_bounds__(kCT) void face_count_kernel(const long long *last_of_face, int nf, int *block_count) {
   __shared__ int wave_cnt[kCT / 64];
@@ -185,10 +196,17 @@ struct DevBuf {
 int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
                     const double *d_vertices, const int *d_faces, const double *d_normals, int nf, const double *leds,
                     const double *view, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
-                    const double *opts, double *d_brdf_surfaces, double *avg, long long *n_pixels, hipStream_t stream) {
+                    const double *opts, double *d_brdf_surfaces, double *avg, long long *n_pixels, hipStream_t stream,
+                    double *d_surface_covar, double *d_surface_stats, int *d_surface_rank) {
+  const bool want_stats = d_surface_covar || d_surface_stats || d_surface_rank;
+  const char *who = want_stats ? "brdf_hip_fit_capture_stats_dev" : "brdf_hip_fit_capture_dev";
   if (!d_images || !d_pixel_map || !d_vertices || !d_faces || !d_normals || !leds || !view || !p0 || !d_brdf_surfaces ||
       L <= 0 || L > 64 || H <= 0 || W <= 0 || nf <= 0) {
-    set_error("brdf_hip_fit_capture_dev(): bad arguments");
+    set_error("%s(): bad arguments", who);
+    return kLmError;
+  }
+  if (want_stats && (L < kM || nf > 0x7fffffff / 3)) {  // before anything runs: a covariance needs n >= 3 samples; the maps have 3 nf rows
+    set_error("%s(): L = %d, nf = %d: the statistics maps need L >= %d images and 3 nf <= 2^31-1", who, L, nf, kM);
     return kLmError;
   }
   (void)hipGetLastError();
@@ -213,7 +231,7 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
   if (avg) avg[0] = avg[1] = avg[2] = 0.0;
   if (S == 0) return 0;
   if (3 * S > 0x7fffffffLL) {
-    set_error("brdf_hip_fit_capture_dev(): %lld pixels carry a face; the batched fitter takes at most 2^31-1 fits per call", S);
+    set_error("%s(): %lld pixels carry a face; the batched fitter takes at most 2^31-1 fits per call", who, S);
     return kLmError;
   }
   CAP_OK(hipMemcpyAsync(offsets.ptr, h_off.data(), sizeof(long long) * nb, hipMemcpyHostToDevice, stream));
@@ -257,6 +275,28 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
   hipLaunchKernelGGL(store_kernel, dim3(sb), dim3(kCT), 0, stream, p.as<double>(), face_s.as<int>(), last.as<long long>(), S,
                      d_brdf_surfaces, sums.as<double>());
   CAP_OK(hipGetLastError());
+  DevBuf src_of_row;
+  if (want_stats) {  // the staged angles / x / p are still in HBM: one pass over the stored fits
+    CAP_OK(src_of_row.alloc(sizeof(int) * 3 * (size_t)nf));
+    hipLaunchKernelGGL(stats_rows_kernel, dim3((3 * nf + kCT - 1) / kCT), dim3(kCT), 0, stream, last.as<long long>(), nf, src_of_row.as<int>());
+    CAP_OK(hipGetLastError());
+    FitStatsArgs fs;
+    fs.method = a.method;
+    fs.model = model;
+    fs.d_angles = a.d_angles;
+    fs.d_x = a.d_x;
+    fs.S = a.S;
+    fs.n = L;
+    fs.d_p = a.d_p;
+    fs.opts = opts;
+    fs.d_covar = d_surface_covar;
+    fs.d_stats = d_surface_stats;
+    fs.d_rank = d_surface_rank;
+    fs.d_src = src_of_row.as<int>();
+    fs.rows = 3 * nf;
+    fs.stream = stream;
+    if (fit_stats_enqueue(fs, who) != 0) return kLmError;
+  }
   std::vector<double> h_sums((size_t)3 * sb);
   CAP_OK(hipMemcpyAsync(h_sums.data(), sums.ptr, sizeof(double) * 3 * sb, hipMemcpyDeviceToHost, stream));
   CAP_OK(hipStreamSynchronize(stream));

@@ -148,6 +148,51 @@ def fit_batch(method: int, model: int, angles, x, p0, *, lb=None, ub=None, itmax
     return p, info, ret
 
 
+@dataclass
+class FitStats:
+    """Per-fit statistics at a fitted point (brdf_hip_fit_stats_batch_dev): torch CUDA tensors, or numpy for numpy inputs."""
+    covar: object  # [S,3,3]  sumsq/(n-3) * inverse(J^T J), J at p
+    stats: object  # [S,8]    sumsq, R2, sd[0..2], rho01, rho02, rho12
+    rank: object   # [S] int32: 3, or 0 where the covariance could not be formed (covar and its six derived values are 0)
+
+
+def fit_stats_batch(method: int, model: int, angles, x, p, *, opts=None) -> FitStats:
+    """Covariance, standard errors, correlations and R^2 of S fits at their fitted points p: one evaluation pass, whoever
+    fitted p.  angles [S,3,n], x [S,n], p [S,3]: CUDA float64 tensors (asynchronous on the current stream), or numpy arrays
+    (host-pointer entry: uploads, runs, downloads).  `method` selects how the Jacobian row is formed (finite differences
+    with opts[4]'s step, or the analytic row); for METHOD_DIF it is the Jacobian at p, not levmar's secant one."""
+    op_a = _f64(opts, 5)
+    if isinstance(x, np.ndarray):
+        angles = np.ascontiguousarray(angles, dtype=np.float64)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        _require(x.ndim == 2, "x must be [S, n]")
+        S, n = x.shape
+        _require(angles.shape == (S, 3, n) and p.shape == (S, 3), "angles must be [S, 3, n], p [S, 3]")
+        covar, stats, rank = np.zeros((S, 3, 3)), np.zeros((S, 8)), np.zeros(S, dtype=np.int32)
+        rc = lib.brdf_hip_fit_stats_batch(method, model, _dptr(angles), _dptr(x), S, n, _dptr(p), _dptr(op_a), _dptr(covar),
+                                          _dptr(stats), rank.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc != 0:
+            raise RuntimeError(f"brdf_hip_fit_stats_batch failed: {last_error()}")
+        return FitStats(covar, stats, rank)
+    import torch
+    _require(angles.is_cuda and x.is_cuda and p.is_cuda and angles.device == x.device == p.device, "angles, x, p: CUDA tensors on one device")
+    _require(angles.dtype == torch.float64 and x.dtype == torch.float64 and p.dtype == torch.float64, "angles, x, p: float64")  # the kernels read raw doubles
+    _require(x.dim() == 2, "x must be [S, n]")
+    S, n = x.shape
+    _require(tuple(angles.shape) == (S, 3, n) and tuple(p.shape) == (S, 3), "angles must be [S, 3, n], p [S, 3]")
+    angles, x, p = angles.contiguous(), x.contiguous(), p.contiguous()
+    covar = torch.zeros((S, 3, 3), dtype=torch.float64, device=x.device)
+    stats = torch.zeros((S, 8), dtype=torch.float64, device=x.device)
+    rank = torch.zeros((S,), dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.brdf_hip_fit_stats_batch_dev(method, model, angles.data_ptr(), x.data_ptr(), S, n, p.data_ptr(), _dptr(op_a),
+                                              covar.data_ptr(), stats.data_ptr(), rank.data_ptr(), _stream_handle(torch))
+    if rc != 0:
+        raise RuntimeError(f"brdf_hip_fit_stats_batch_dev failed: {last_error()}")
+    return FitStats(covar, stats, rank)
+
+
 def fit_batch_multi(method: int, model: int, angles, x, p0, *, devices=None, lb=None, ub=None, itmax=100, opts=None):
     """S independent fits over several GPUs of this process (brdf_hip_fit_batch_multi): HOST arrays angles [S,3,n], x [S,n],
     p0 [S,3] (not modified).  `devices`: HIP ordinals, one contiguous shard of ceil(S/len) fits each (dist.shard_range; an
@@ -250,10 +295,13 @@ def cosines(vertices, faces, face_normals, leds, view_origin, *, surfels=None, r
 
 def fit_capture(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, rv_mode: int = 0,
                 p0=(0.5, 1.0, 1.0), lb=(0.0, 0.0, 0.0), ub=(100.0, 100.0, 100.0), itmax: int = 100, opts=None, brdf_surfaces=None,
-                validate: bool = True):
+                validate: bool = True, want_stats: bool = False, surface_stats: FitStats | None = None):
     """The pixel loop of CBRDFdata::CalcBRDFEquation (brdfdata.cpp:1188-1227) on the device.  images: CUDA uint8
     [L,H,W,3] (BGR), pixel_map: CUDA int32 [H,W] (face index or -1), mesh as in cosines().  Returns (brdf_surfaces
-    CUDA float64 [nf,3,3] = {kd,ks,n} per face and channel, avg[3], number of pixels that carried a face)."""
+    CUDA float64 [nf,3,3] = {kd,ks,n} per face and channel, avg[3], number of pixels that carried a face).
+    want_stats=True (brdf_hip_fit_capture_stats_dev): a fourth value, FitStats with covar [nf,3,3,3], stats [nf,3,8],
+    rank [nf,3] of the fits that were stored (`surface_stats`: maps to write into; faces no pixel carries keep their
+    values, zeros by default)."""
     import torch
     images, pixel_map = images.contiguous(), pixel_map.contiguous()
     vertices, faces, face_normals = vertices.contiguous(), faces.contiguous(), face_normals.contiguous()
@@ -275,14 +323,31 @@ def fit_capture(model: int, images, pixel_map, vertices, faces, face_normals, le
     oa = _f64(opts, 5) if opts is not None else None
     avg = np.zeros(3)
     npx = C.c_longlong(0)
+    args = (model, images.data_ptr(), L, H, W, pixel_map.data_ptr(), vertices.data_ptr(), faces.data_ptr(), face_normals.data_ptr(),
+            nf, _dptr(la), _dptr(va), rv_mode, _dptr(pa), _dptr(lba), _dptr(uba), itmax, _dptr(oa) if oa is not None else None,
+            brdf_surfaces.data_ptr(), _dptr(avg), C.byref(npx))
+    if not want_stats:
+        with torch.cuda.device(images.device):
+            rc = lib.brdf_hip_fit_capture_dev(*args, _stream_handle(torch))
+        if rc != 0:
+            raise RuntimeError(f"brdf_hip_fit_capture_dev failed: {last_error()}")
+        return brdf_surfaces, avg, npx.value
+    st = surface_stats
+    if st is None:
+        st = FitStats(torch.zeros((nf, 3, 3, 3), dtype=torch.float64, device=images.device),
+                      torch.zeros((nf, 3, 8), dtype=torch.float64, device=images.device),
+                      torch.zeros((nf, 3), dtype=torch.int32, device=images.device))
+    _require(tuple(st.covar.shape) == (nf, 3, 3, 3) and tuple(st.stats.shape) == (nf, 3, 8) and tuple(st.rank.shape) == (nf, 3),
+             "surface_stats: covar [nf,3,3,3], stats [nf,3,8], rank [nf,3]")
+    _require(st.covar.dtype == torch.float64 and st.stats.dtype == torch.float64 and st.rank.dtype == torch.int32,
+             "surface_stats: float64 covar and stats, int32 rank")
+    _require(st.covar.is_contiguous() and st.stats.is_contiguous() and st.rank.is_contiguous() and st.covar.is_cuda and st.stats.is_cuda
+             and st.rank.is_cuda, "surface_stats: contiguous CUDA tensors")
     with torch.cuda.device(images.device):
-        rc = lib.brdf_hip_fit_capture_dev(model, images.data_ptr(), L, H, W, pixel_map.data_ptr(), vertices.data_ptr(),
-                                          faces.data_ptr(), face_normals.data_ptr(), nf, _dptr(la), _dptr(va), rv_mode,
-                                          _dptr(pa), _dptr(lba), _dptr(uba), itmax, _dptr(oa) if oa is not None else None,
-                                          brdf_surfaces.data_ptr(), _dptr(avg), C.byref(npx), _stream_handle(torch))
+        rc = lib.brdf_hip_fit_capture_stats_dev(*args, _stream_handle(torch), st.covar.data_ptr(), st.stats.data_ptr(), st.rank.data_ptr())
     if rc != 0:
-        raise RuntimeError(f"brdf_hip_fit_capture_dev failed: {last_error()}")
-    return brdf_surfaces, avg, npx.value
+        raise RuntimeError(f"brdf_hip_fit_capture_stats_dev failed: {last_error()}")
+    return brdf_surfaces, avg, npx.value, st
 
 
 def fit_capture_single(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, rv_mode: int = 0,

@@ -223,6 +223,33 @@ int brdf_hip_fit_batch_multi(int method, int model, const double *angles, const 
  * run, e.g. an empty shard); returns 0, or LM_ERROR if `shard` is out of range */
 int brdf_hip_last_multi_stats(int shard, int *device, long long *first, long long *count, double *ms3);
 
+/* ---- per-fit statistics at a fitted point (extensions) ------------------------------------------------------ */
+/* What a single fit returns through `covar` and levmar's utilities, for S fits at once: one evaluation pass over the
+ * samples of every fit at the point d_p[s] (kernels of their own, fit_stats.hip; the fit kernels are not involved).
+ *   covar[s] = sumsq / (n - 3) * inverse(J^T J), levmar's LEVMAR_COVAR (misc_core.c:564-591, the same Crout LU), with
+ *     J the Jacobian AT d_p[s] as `method` forms it -- BRDF_METHOD_DIF / _BC_DIF: finite differences with levmar's steps
+ *     (delta = |opts[4]|, central when opts[4] < 0; opts == NULL: forward, LM_DIFF_DELTA), BRDF_METHOD_BC_DER / _DER: the
+ *     analytic rows of BRDFJac_hip -- and sumsq = sum (x - f(p))^2.  For a converged dlevmar_bc_dif / _bc_der / _der fit
+ *     this is the covariance levmar itself returns (it inverts the J^T J of its last iteration's point).  For dlevmar_dif
+ *     it is the Jacobian at p, NOT levmar's secant (Broyden-updated) one, whose value depends on the path of the fit.
+ *   stats[s] = { sumsq, R2, sd[0], sd[1], sd[2], rho01, rho02, rho12 }: R2 = 1 - sumsq / sum (x - mean x)^2 as dlevmar_R2
+ *     (misc_core.c:616-658; the IEEE result when x is constant), sd[i] = sqrt(covar[i][i]) and rho_ij = covar[i][j] /
+ *     sqrt(covar[i][i] covar[j][j]): dlevmar_stddev / dlevmar_corcoef on the returned covar[s] give the same values.
+ *   rank[s] = 3, or 0 where J^T J has a zero row or any input or result is not finite; then covar[s] and the six
+ *     values derived from it are 0.0 (what a single fit's covar shows in that case); sumsq and R2 are still written.
+ * d_angles[S][3][n], d_x[S][n], d_p[S][3] (read only), d_covar[S][9], d_stats[S][BRDF_STATS_SZ], d_rank[S]: DEVICE
+ * pointers, each output may be NULL (not all three); opts (5 or NULL): HOST, only opts[4] is read.  n >= 3.  All sums are
+ * fixed-order trees: two calls give the same bits, and a fit's result does not depend on S or on its place in the batch.
+ * Asynchronous on `stream`.  Arguments are checked before any HIP call.  Returns 0, or LM_ERROR with a message in
+ * brdf_hip_last_error().  Not covered: dscl, weights, a multi-GPU variant (call the host-pointer entry per device). */
+#define BRDF_STATS_SZ 8
+int brdf_hip_fit_stats_batch_dev(int method, int model, const double *d_angles, const double *d_x, int S, int n,
+                                 const double *d_p, const double *opts, double *d_covar, double *d_stats, int *d_rank,
+                                 void *stream);
+/* the same with HOST pointers: uploads, runs, downloads, synchronises */
+int brdf_hip_fit_stats_batch(int method, int model, const double *angles, const double *x, int S, int n, const double *p,
+                             const double *opts, double *covar, double *stats, int *rank);
+
 /* hx[i] = model(p; sample i) for device-resident planes; d_hx DEVICE pointer, p HOST pointer. */
 int brdf_hip_model_eval_dev(int model, const double *d_angles, int n, const double *p, double *d_hx,
                             void *stream);
@@ -267,6 +294,19 @@ int brdf_hip_fit_capture_dev(int model, const unsigned char *d_images, int L, in
                              const double *leds, const double *view_origin, int rv_mode, const double *p0, const double *lb,
                              const double *ub, int itmax, const double *opts, double *d_brdf_surfaces, double *avg,
                              long long *n_pixels, void *stream);
+
+/* brdf_hip_fit_capture_dev followed by the statistics pass of brdf_hip_fit_stats_batch_dev (BRDF_METHOD_BC_DIF, the call's
+ * opts) over the fits it stored: d_surface_covar[nf][3][9], d_surface_stats[nf][3][BRDF_STATS_SZ], d_surface_rank[nf][3]
+ * (DEVICE, each may be NULL) receive, per face and channel, the statistics of the fit whose {kd, ks, n} went into
+ * d_brdf_surfaces -- the face's LAST pixel.  Faces no pixel carries are left untouched in all maps.  d_brdf_surfaces, avg
+ * and n_pixels are bit-identical to brdf_hip_fit_capture_dev's.  (The single-BRDF capture below already returns info[]; its
+ * covariance is available through brdf_hip_fit_channels_dev.) */
+int brdf_hip_fit_capture_stats_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                   const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf,
+                                   const double *leds, const double *view_origin, int rv_mode, const double *p0,
+                                   const double *lb, const double *ub, int itmax, const double *opts, double *d_brdf_surfaces,
+                                   double *avg, long long *n_pixels, void *stream, double *d_surface_covar,
+                                   double *d_surface_stats, int *d_surface_rank);
 
 /* Replaces CBRDFdata::CalcBRDFEquation_SingleBRDF (brdfdata.cpp:1138-1186) with SolveEquation_SingleBRDF (:992-1062): ONE
  * {kd, ks, n} per colour channel for the whole object, fitted with dlevmar_bc_dif to the L samples of every face the pixel
