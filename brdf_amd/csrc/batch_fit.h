@@ -38,6 +38,7 @@ struct BatchCtx {
   int analytic;  // RQ_JAC rows from the model's analytic Jacobian (dlevmar_bc_der / dlevmar_der) instead of finite differences
   int chain;     // dlevmar_dif: trial points per sweep in a chain of rejections (eight-wave kernel; 1 = one at a time)
   int spec_jac;  // dlevmar_bc_dif: candidates evaluated by Jacobian passes (off in the batched kernels: they are bound by arithmetic)
+  int dif_fused; // dlevmar_dif, eight-wave kernel: the step behind a trial pass tries DifMachine::fused_trial_step first
   double opts[5], lb[kM], ub[kM];
 };
 

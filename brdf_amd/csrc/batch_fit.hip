@@ -719,6 +719,7 @@ int batch_fit_launches(const BatchFitArgs &a, const Geometry &g, int *flags, int
   c.multi = (g.threads == 512) ? 1 : pg_candidates();
   c.chain = 1;     // (only the eight-wave kernel compiles the chains in)
   c.spec_jac = 0;  // batched fits are bound by arithmetic: a Jacobian pass that is not used costs three evaluations
+  c.dif_fused = dif_fused_enabled() ? 1 : 0;
   for (int i = 0; i < 5; ++i) c.opts[i] = a.opts ? a.opts[i] : 0.0;
   for (int i = 0; i < kM; ++i) {
     c.lb[i] = a.lb ? a.lb[i] : 0.0;

@@ -172,12 +172,12 @@ constexpr int kTrialSums = 3 + 2 * kM;  // what a dlevmar_dif trial sweep reduce
 // ... and what the machine wants (SumLayout::DIF_TRIAL: [e'^2, J'^T J' lower (6), J'^T e' (3), J'^T e (3)]), from them and from the
 // products of the CURRENT Jacobian the machine holds while a trial is out: jtj (its diagonal carries mu: the plain one is in
 // diag) and jte.  Executed by the control wave, all lanes the same values; in place.
+// expand_trial_sums_to: into out[SumLayout::DIF_TRIAL], a local array of the caller (registers); expand_trial_sums: in place.
 template <class Core, class Cool>
-__device__ __forceinline__ void expand_trial_sums(const Core &core, const Cool &cool, const double *dpv, double *sums) {
+__device__ __forceinline__ void expand_trial_sums_to(const Core &core, const Cool &cool, const double *dpv, const double *sums, double *out) {
   const double s0 = sums[0], a[kM] = {sums[1], sums[2], sums[3]}, b = sums[1 + kM];
   const double d[kM] = {sums[2 + kM], sums[3 + kM], sums[4 + kM]}, te = sums[2 + 2 * kM];
   const double dp[kM] = {dpv[0], dpv[1], dpv[2]};
-  double out[SumLayout<kM>::DIF_TRIAL];
   out[0] = s0;
   int c = 1;
 #pragma unroll
@@ -194,8 +194,25 @@ __device__ __forceinline__ void expand_trial_sums(const Core &core, const Cool &
     out[1 + kNL + j] = d[j];
     out[1 + kNL + kM + j] = fma(dp[j], te, core.jte[j]);
   }
+}
+template <class Core, class Cool>
+__device__ __forceinline__ void expand_trial_sums(const Core &core, const Cool &cool, const double *dpv, double *sums) {
+  double out[SumLayout<kM>::DIF_TRIAL];
+  expand_trial_sums_to(core, cool, dpv, sums, out);
 #pragma unroll
   for (int j = 0; j < SumLayout<kM>::DIF_TRIAL; ++j) sums[j] = out[j];
+}
+
+// The control wave's step behind a dlevmar_dif trial pass, tried before the machine's generic run(): the NINE reduced sums are
+// expanded in registers and handed to DifMachine::fused_trial_step, which judges the trial, solves and issues the next trial
+// in one straight-line block (lm_machine.h).  false: nothing was written (sums[] included) -- expand_trial_sums + run() as ever.
+template <class Machine>
+__device__ __forceinline__ bool fused_trial_step_device(const typename Machine::Cold &c, typename Machine::CoreInts &hi, typename Machine::CoreReals &h,
+                                                        typename Machine::Cool &cool, Request<kM> &req, const double *sums, const double *dpv) {
+  if (hi.phase != Machine::D_AFTER_TRIAL) return false;
+  double out[SumLayout<kM>::DIF_TRIAL];
+  expand_trial_sums_to(h, cool, dpv, sums, out);
+  return Machine::template fused_trial_step<true, true>(c, hi, h, cool, req, out);
 }
 
 

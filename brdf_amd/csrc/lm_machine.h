@@ -469,6 +469,128 @@ struct DifMachine {
     }
   }
 
+  // The transition most steps of a fit are (60-87 % of them, every model and size tried): a speculative trial has been
+  // judged -- accepted, or rejected with the Broyden update adopted -- and the next plain trial goes out.  run() walks
+  // D_AFTER_TRIAL -> D_DECIDE (-> D_REJECT) -> D_ITER_TOP -> D_GRADIENT -> D_SOLVE for it, and on an LDS-resident machine
+  // every phase reads its inputs from the machine and writes its outputs back for the next phase to read again.  Here the
+  // same floating-point operations, in the same order on the same operands, run as ONE straight-line block on locals:
+  // every input is loaded once, nothing is stored until every test the chain makes on the way has passed, and the stores
+  // at the end leave in EVERY field what the chain would have left (tests/cpp/dif_fused_harness.cpp compares the whole
+  // state after every step).  Anything else -- a stop, a fresh Jacobian due, a rejection without an update, a failed
+  // solve -- returns false with the machine untouched, and run() does the step: the rare paths exist once.
+  // s: the trial pass's sums (SumLayout::DIF_TRIAL); never aliases the machine (callers pass a local array or sums[]).
+  template <bool ONE_LANE = false, bool MULTI = false>
+  static LM_HD bool fused_trial_step(const Cold &c, CoreInts &hi, CoreReals &h, Cool &cool, Request<M, Real> &req, const Real *s) {
+    constexpr int NL = SumLayout<M>::NL;
+    if (hi.phase != D_AFTER_TRIAL || !c.speculative || hi.stop) return false;
+    // ---- D_AFTER_TRIAL
+    const Real e2 = s[0], p_e2 = h.p_e2;
+    const Real dF = p_e2 - e2;
+    Real mu = h.mu;
+    Real dL = Real(0.0);
+    for (int i = 0; i < M; ++i) dL += h.dp[i] * (mu * h.dp[i] + h.jte[i]);
+    int acc = (dL > Real(0.0) && dF > Real(0.0)) ? 1 : 0;
+    int ok = (lm_finite(e2) && (hi.updp || dF > 0)) ? 1 : 0;  // (Sum e'^2 finite; `updated`: the Broyden update is adopted)
+    if (ONE_LANE) {
+      acc = lm_uniform(acc);
+      ok = lm_uniform(ok);
+    }
+    if (!ok) return false;
+    // ---- D_DECIDE / D_REJECT
+    Real pn[M], pe2n;
+    int nu, updp;
+    if (acc) {
+      Real t = (Real(2.0) * dF / dL - Real(1.0));
+      t = Real(1.0) - t * t * t;
+      mu = mu * ((t >= Real(kOneThird)) ? t : Real(kOneThird));
+      nu = 2;
+      for (int i = 0; i < M; ++i) pn[i] = cool.pdp[i];
+      pe2n = e2;
+      updp = 1;
+    } else {
+      mu *= hi.nu;
+      nu = (int)((unsigned)hi.nu << 1);
+      if (nu <= hi.nu) return false;
+      for (int i = 0; i < M; ++i) pn[i] = h.p[i];
+      pe2n = p_e2;
+      updp = hi.updp;
+    }
+    // ---- D_ITER_TOP
+    const int k1 = hi.k + 1, updjac1 = hi.updjac + 1;
+    if (!(k1 < c.itmax) || k1 == 0) return false;  // (k1 == 0 cannot happen: D_SOLVE would seed mu)
+    if ((updp && nu > 16) || updjac1 == c.refresh) return false;
+    const int chain1 = MULTI ? 0 : hi.chain;  // (`updated` holds)
+    if (MULTI && c.multi > 1 && updp == 0 && chain1 >= 1 && !hi.single) return false;  // (D_SOLVE's chain of candidates: never)
+    // ---- D_GRADIENT with the sums of the updated Jacobian
+    const Real *g = s + 1 + NL + (acc ? 0 : M);
+    Real A[M * M], b[M], diag[M];
+    unpack_lower<M>(s + 1, A);
+    Real p_l2 = Real(0.0), jte_inf = Real(0.0);
+    for (int i = 0; i < M; ++i) {
+      b[i] = g[i];
+      const Real t = lm_abs(b[i]);
+      if (jte_inf < t) jte_inf = t;
+      diag[i] = A[i * M + i];
+      p_l2 += pn[i] * pn[i];
+    }
+    ok = (!(pe2n <= c.o.eps3) && !(jte_inf <= c.o.eps1)) ? 1 : 0;
+    if (ONE_LANE) ok = lm_uniform(ok);
+    if (!ok) return false;
+    // ---- D_SOLVE
+    Real Am[M * M], dpn[M], pdpn[M];
+    for (int i = 0; i < M * M; ++i) Am[i] = A[i];
+    for (int i = 0; i < M; ++i) Am[i * M + i] += mu;
+    ok = lu_solve<M>(Am, b, dpn);
+    Real dp_l2 = Real(0.0);
+    for (int i = 0; i < M; ++i) {
+      const Real t = dpn[i];
+      pdpn[i] = pn[i] + t;
+      dp_l2 += t * t;
+    }
+    ok = (ok && !(dp_l2 <= c.o.eps2sq * p_l2) && !(dp_l2 >= (p_l2 + c.o.eps2) / (Real(kEpsilon) * Real(kEpsilon)))) ? 1 : 0;
+    if (ONE_LANE) ok = lm_uniform(ok);
+    if (!ok) return false;
+    // ---- every test has passed: commit
+    hi.k = k1;
+    hi.nu = nu;
+    ++hi.nfev;
+    ++hi.nlss;
+    hi.updjac = updjac1;
+    hi.updp = updp;
+    hi.newjac = 0;
+    if (acc) hi.sel_hx ^= 1;
+    hi.sel_j ^= 1;
+    hi.accepted = acc;
+    if (MULTI) hi.chain = hi.single = 0;
+    h.mu = mu;
+    h.p_e2 = pe2n;
+    h.jte_inf = jte_inf;
+    h.p_l2 = p_l2;
+    h.dp_l2 = dp_l2;
+    h.pdp_e2 = e2;
+    for (int i = 0; i < M * M; ++i) {
+      h.jtj[i] = Am[i];
+      cool.spec_jtj[i] = A[i];
+    }
+    for (int i = 0; i < M; ++i) {
+      h.p[i] = pn[i];
+      h.jte[i] = b[i];
+      h.dp[i] = dpn[i];
+      cool.diag[i] = diag[i];
+      cool.pdp[i] = pdpn[i];
+      cool.spec_jte[i] = b[i];
+    }
+    clear_req(hi, req);
+    req.kind = RQ_DIF_TRIAL;
+    for (int i = 0; i < M; ++i) {
+      req.p[i] = pn[i];
+      req.q[i] = pdpn[i];
+      req.dp[i] = dpn[i];
+    }
+    req.dp_l2 = dp_l2;
+    return true;
+  }
+
   // ONE_LANE: the caller guarantees that exactly one lane of the wave executes this step (see lm_uniform)
   // MULTI: compiles the multi-candidate rejection chains in (Cold::multi > 1 turns them on)
   template <bool ONE_LANE = false, bool MULTI = false>

@@ -88,6 +88,7 @@ int resident_attempt(const ResidentKernels &k, bool fast, const StreamFitArgs &a
   c.multi = pg_candidates();
   c.chain = dif_chain_candidates();
   c.spec_jac = bc_spec_jac_enabled() ? 1 : 0;
+  c.dif_fused = dif_fused_enabled() ? 1 : 0;
   c.analytic = a.analytic ? 1 : 0;
   c.mbox = ws.d_mbox;
   c.n = a.n;

@@ -88,6 +88,7 @@ struct ResidentCtx {
   int itmax, has_opts, has_lb, has_ub, has_dscl, want_covar, multi, analytic;
   int chain;     // dlevmar_dif: trial points per sweep in a chain of rejections (DifMachine::Cold::multi)
   int spec_jac;  // dlevmar_bc_dif / bc_der: candidates evaluated by Jacobian passes (BcMachine::Cold::spec_jac)
+  int dif_fused; // dlevmar_dif: the step behind a trial pass tries DifMachine::fused_trial_step first (BRDF_HIP_DIF_FUSED, default on)
   Mailbox *mbox;
   int n;
   unsigned tag_base;  // tags of this launch are tag_base + epoch + 1: the rows need no zeroing between launches
@@ -912,7 +913,9 @@ __global__ __launch_bounds__(kRThreads) void resident_fit_kernel(ResidentCtx ctx
       ints_regs = sm.h;
       Machine::uniform_ints(ints_regs);
     }
-    (void)cold0, (void)ints_regs;
+    const int fused = (METHOD == 0) ? (BATCHED ? bctx.dif_fused : ctx.dif_fused) : 0;
+    int n_fused = 0;  // steps fused_trial_step took (reported in the mailbox's stamps[0])
+    (void)cold0, (void)ints_regs, (void)fused;
     const long long t_first = (long long)wall_clock64();
     unsigned epoch = 0;
     for (;; ++epoch) {
@@ -978,15 +981,25 @@ __global__ __launch_bounds__(kRThreads) void resident_fit_kernel(ResidentCtx ctx
         __syncthreads();  // B (the other waves read s_abort behind it)
         return;
       }
+      bool stepped = false;
       if (kind == RQ_DIF_TRIAL) {
         if constexpr (METHOD == 0) {
-          expand_trial_sums(static_cast<const typename Machine::Core &>(sm.h), sm.h.cool, su.dp, sums);
+          // trial judged -> next trial, most steps of a fit: one straight-line block on registers (lm_machine.h:
+          // fused_trial_step; nothing of it is live outside this block).  Declined: the machine and sums[] are untouched.
+          if (fused) {
+            stepped = fused_trial_step_device<Machine>(cold0, ints_regs, static_cast<typename Machine::CoreReals &>(sm.h), sm.h.cool, sm.h.req, sums, su.dp);
+            if (stepped) {
+              ++n_fused;
+              Machine::uniform_ints(ints_regs);
+            }
+          }
+          if (!stepped) expand_trial_sums(static_cast<const typename Machine::Core &>(sm.h), sm.h.cool, su.dp, sums);
         }
 #pragma unroll
         for (int j = 0; j < kM; ++j) dp_prev[j] = su.dp[j];
         dp_prev[kM] = su.dp_l2;
       }
-      {  // the LM step, on the machine in LDS
+      if (!stepped) {  // the LM step, on the machine in LDS
         if constexpr (METHOD == 0) {  // (+ chains of rejections, several trial points to a sweep)
           typename Machine::Cold cc;  // (results are written by the finishing step only and stored right behind it: nothing carried)
           cc.itmax = cold0.itmax, cc.n = cold0.n, cc.want_covar = cold0.want_covar, cc.refresh = cold0.refresh;
@@ -1045,6 +1058,7 @@ __global__ __launch_bounds__(kRThreads) void resident_fit_kernel(ResidentCtx ctx
       mb->n_eval = (long long)epoch - n_jac;
       mb->t_first = t_first;
       mb->t_last = (long long)wall_clock64();
+      st_[0] = n_fused;  // (slot 0 carries no time stamp)
       for (int k = 0; k < 8; ++k) mb->stamps[k] = st_[k];
       for (int i = 0; i < kM; ++i) mb->p[i] = sm.h.p[i];
       for (int i = 0; i < kInfoSz; ++i) mb->info[i] = sm.c.info[i];

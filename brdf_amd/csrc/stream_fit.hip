@@ -657,6 +657,13 @@ int dif_chain_candidates() {
   return k < 1 ? 1 : (k > kMaxCand ? kMaxCand : k);
 }
 
+// BRDF_HIP_DIF_FUSED=0: the resident dlevmar_dif kernels step every pass with the machine's generic run() (default: the step behind
+// a trial pass tries the fused trial -> trial transition first, lm_machine.h: DifMachine::fused_trial_step; same results)
+bool dif_fused_enabled() {
+  const char *e = getenv("BRDF_HIP_DIF_FUSED");
+  return !(e && e[0] == '0');
+}
+
 // BRDF_HIP_SPEC_JAC=0: single dlevmar_bc_dif / bc_der fits evaluate their candidates by plain evaluation passes (default: by
 // Jacobian passes, lm_machine.h: BcMachine::Cold::spec_jac)
 bool bc_spec_jac_enabled() {

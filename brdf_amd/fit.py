@@ -439,7 +439,11 @@ def last_fit_stats() -> dict:
     a, b, c = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
     us = C.c_double(0.0)
     lib.brdf_hip_last_fit_stats(C.byref(a), C.byref(b), C.byref(c), C.byref(us))
-    return {"passes": a.value, "jac_passes": b.value, "eval_passes": c.value, "device_us": us.value,
+    st = (C.c_longlong * 8)()
+    lib.brdf_hip_last_fit_stamps(st)
+    # fused_steps: LM steps the resident dlevmar_dif kernel took through DifMachine::fused_trial_step (the mailbox's stamps[0],
+    # which carries no time stamp; 0 for every other regime and with BRDF_HIP_DIF_FUSED=0)
+    return {"passes": a.value, "jac_passes": b.value, "eval_passes": c.value, "device_us": us.value, "fused_steps": int(st[0]),
             "launches": lib.brdf_hip_last_fit_launches(), "kernel_us": lib.brdf_hip_last_fit_kernel_us()}
 
 
