@@ -9,7 +9,6 @@
 // sweep over the lane's SPT cached samples followed by a DPP/LDS workgroup reduction; the scalar LM
 // state machine (lm_machine.h) lives in LDS and is stepped by lane 0.  Fits finish after different
 // numbers of passes; the hardware workgroup scheduler backfills, which is the load balancing.
-#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 #include <vector>
@@ -597,24 +596,20 @@ BatchFn kernel_for(const Geometry &g, int model, int method, bool fast) {
 // stream -- must not touch the scratch before the previous call's launches have finished with it: every call waits
 // (device-side, hipStreamWaitEvent) on the event the previous call recorded behind its last launch.
 struct BatchScratch {
-  int *ptr = nullptr;
-  size_t cap = 0;  // ints, without the two queue words
-  int device = -1;
+  DeviceBlock<int> block;  // flags[fits()], then the two queue words
   hipEvent_t last_use = nullptr;
   bool in_use = false;
-  // a host thread that ends gives its block back, on the block's device, once its last batch is done with it
-  ~BatchScratch() {
-    if (!ptr) return;
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    if (cur != device) (void)hipSetDevice(device);
-    if (last_use) {
-      (void)hipEventSynchronize(last_use);
-      (void)hipEventDestroy(last_use);
-    }
-    (void)hipFree(ptr);
-    if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
+  size_t fits() const { return block.cap - 2; }
+  // on the block's device, once everything queued there -- this thread's last batch included -- is done with it
+  void release() {
+    if (!block.ptr) return;
+    DeviceScope on(block.device);
+    block.release();
+    if (last_use) (void)hipEventDestroy(last_use);
+    last_use = nullptr;
+    in_use = false;
   }
+  ~BatchScratch() { release(); }  // a host thread that ends gives its block back
 };
 thread_local BatchScratch g_scratch;
 
@@ -640,68 +635,31 @@ RowsFn rows_kernel(int model, int method, bool fast) {
 //   dlevmar_bc_dif  rows kernel 2.99e6 / 1.27e6,        wave per fit 3.95e6 / 2.09e6 -> wave per fit: bc_dif's long,
 //                   divergent steps (line search, projected gradient) serialise over the four row leaders, and the
 //                   wave-per-fit kernel evaluates up to 8 projected-gradient candidates per pass
-// BRDF_HIP_ROWS=0: never the rows kernel; BRDF_HIP_ROWS=1: the rows kernel for both entry points.
-bool rows_path_enabled(int method) {
-  const char *e = getenv("BRDF_HIP_ROWS");
-  if (e && e[0] == '0') return false;
-  if (e && e[0] == '1') return true;
-  return method == 0;
-}
+// (fit_switches.h: rows_path_enabled, BRDF_HIP_ROWS)
 
 // four fits per wavefront, rows pull work from a queue: a few waves per SIMD on every CU are enough
-int rows_enqueue(const BatchFitArgs &a, const BatchCtx &c, bool fast, int *queue) {
+int rows_enqueue(int model, int machine, const BatchCtx &c, bool fast, int *queue, hipStream_t stream) {
   int dev = 0, cus = 0;
   HIP_OK(hipGetDevice(&dev));
   HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
   long long waves = (long long)cus * 16;  // 4 waves per SIMD
-  const long long need = ((long long)a.S + kRowsPerWave - 1) / kRowsPerWave;
+  const long long need = ((long long)c.S + kRowsPerWave - 1) / kRowsPerWave;
   if (waves > need) waves = need;
-  if (fast) {
-    hipLaunchKernelGGL(rows_kernel(a.model, a.method, true), dim3((unsigned)waves), dim3(kWave), 0, a.stream, c, queue);
-    HIP_OK(hipGetLastError());
-    if (a.model != MODEL_WARD) {
-      hipLaunchKernelGGL(rows_kernel(a.model, a.method, false), dim3((unsigned)waves), dim3(kWave), 0, a.stream, c, queue + 1);
-      HIP_OK(hipGetLastError());
-    }
-  } else {
-    HIP_OK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.flags), kNeedsExact, (size_t)a.S, a.stream));
-    hipLaunchKernelGGL(rows_kernel(a.model, a.method, false), dim3((unsigned)waves), dim3(kWave), 0, a.stream, c, queue);
-    HIP_OK(hipGetLastError());
-  }
-  return 0;
-}
-
-// n <= 16, dlevmar_bc_dif: one lane per fit (lane_fit.hip).  Measured (2^20 fits of 16 samples): see DESIGN.md section 6.
-// BRDF_HIP_LANE=0: the wave-per-fit / rows kernels of this file instead.
-bool lane_path_enabled() {
-  const char *e = getenv("BRDF_HIP_LANE");
-  return !(e && e[0] == '0');
+  return launch_fast_then_exact(fast, model != MODEL_WARD, c.flags, (size_t)c.S, queue, stream, [&](bool fast_kernel, int *q) {
+    hipLaunchKernelGGL(rows_kernel(model, machine, fast_kernel), dim3((unsigned)waves), dim3(kWave), 0, stream, c, q);
+  });
 }
 
 }  // namespace
 
-// BRDF_HIP_BATCH_BIG=0: the symmetric 512 x 8 geometry of this file instead of the control-wave kernel for 1024 < n <= 4096
-// BRDF_HIP_BATCH_DIF_CHAIN=k: the eight-wave batched dlevmar_dif kernel's trial points per sweep in a chain of rejections
-// (default: the single fits' setting, BRDF_HIP_DIF_CHAIN)
-static int batch_dif_chain() {
-  const char *e = getenv("BRDF_HIP_BATCH_DIF_CHAIN");
-  if (!e) return dif_chain_candidates();
-  const int k = atoi(e);
-  return k < 1 ? 1 : (k > kMaxCand ? kMaxCand : k);
-}
-
-static bool big_path_enabled() {
-  const char *e = getenv("BRDF_HIP_BATCH_BIG");
-  return !(e && e[0] == '0');
-}
-
 namespace {
-int batch_fit_launches(const BatchFitArgs &a, const Geometry &g, int *flags, int *queue) {
-  // the C ABI's method -> the kernels' machine (0 Dif, 1 Bc, 2 Der) + where the Jacobian rows come from
-  const int method = (a.method == BRDF_METHOD_BC_DER) ? 1 : (a.method == BRDF_METHOD_DER ? 2 : a.method);
+// chooses the kernel (ms: a.method's).  n <= kLaneMaxN, dlevmar_bc_dif: one lane per fit (lane_fit.hip; measured, 2^20 fits of 16
+// samples: DESIGN.md section 6)
+int batch_fit_launches(const BatchFitArgs &a, MethodSpec ms, const Geometry &g, int *flags, int *queue) {
+  const int method = ms.machine;
   BatchCtx c;
   memset(&c, 0, sizeof c);
-  c.analytic = (a.method == BRDF_METHOD_BC_DER || a.method == BRDF_METHOD_DER) ? 1 : 0;
+  c.analytic = ms.analytic ? 1 : 0;
   c.angles = a.d_angles;
   c.x = a.d_x;
   c.p = a.d_p;
@@ -716,10 +674,10 @@ int batch_fit_launches(const BatchFitArgs &a, const Geometry &g, int *flags, int
   c.has_ub = a.ub != nullptr;
   // projected-gradient candidates per sweep: pays where the LM step dominates a pass; the 512 x 8 geometry would
   // spill its register-resident samples with 8 unrolled candidates (measured 2.4x slower), so it stays at one
-  c.multi = (g.threads == 512) ? 1 : pg_candidates();
+  c.multi = (g.threads == 512) ? 1 : (int)switch_number(kSwPgMulti);
   c.chain = 1;     // (only the eight-wave kernel compiles the chains in)
   c.spec_jac = 0;  // batched fits are bound by arithmetic: a Jacobian pass that is not used costs three evaluations
-  c.dif_fused = dif_fused_enabled() ? 1 : 0;
+  c.dif_fused = switch_on(kSwDifFused) ? 1 : 0;
   for (int i = 0; i < 5; ++i) c.opts[i] = a.opts ? a.opts[i] : 0.0;
   for (int i = 0; i < kM; ++i) {
     c.lb[i] = a.lb ? a.lb[i] : 0.0;
@@ -727,33 +685,18 @@ int batch_fit_launches(const BatchFitArgs &a, const Geometry &g, int *flags, int
   }
   HIP_OK(hipMemsetAsync(queue, 0, 2 * sizeof(int), a.stream));
   const bool fast = brdf_fast_path_enabled() || a.model == MODEL_WARD;
-  if (a.n <= kLaneMaxN && method == 1 && lane_path_enabled()) return lane_fit_enqueue(a.model, fast, c, queue, a.stream);
-  if (a.n <= kRowLanes && method != 2 && !c.analytic && rows_path_enabled(method)) {
-    BatchFitArgs b = a;
-    b.method = method;
-    return rows_enqueue(b, c, fast, queue);
-  }
-  if (g.threads == 512 && (big_path_enabled() || method == 2 || c.analytic)) {  // 1024 < n <= 4096: eight waves per fit (resident_fit.hip)
-    c.multi = pg_candidates();
+  if (a.n <= kLaneMaxN && method == kBcMachine && switch_on(kSwLane)) return lane_fit_enqueue(a.model, fast, c, queue, a.stream);
+  if (a.n <= kRowLanes && method != kDerMachine && !c.analytic && rows_path_enabled(method == kDifMachine))
+    return rows_enqueue(a.model, method, c, fast, queue, a.stream);
+  if (g.threads == 512 && (switch_on(kSwBatchBig) || method == kDerMachine || c.analytic)) {  // 1024 < n <= 4096: eight waves per fit (resident_fit.hip)
+    c.multi = (int)switch_number(kSwPgMulti);
     c.chain = batch_dif_chain();
-    if (!fast) HIP_OK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags), kNeedsExact, (size_t)a.S, a.stream));
     return resident_batch_enqueue(a.model, method, fast, c, a.stream);
   }
-  const dim3 grid(a.S), block(g.threads);
-  if (fast) {
-    hipLaunchKernelGGL(kernel_for(g, a.model, method, true), grid, block, 0, a.stream, c);
-    HIP_OK(hipGetLastError());
-    if (a.model != MODEL_WARD) {  // fits with a cosine <= 0 marked themselves: second launch on the exact path
-      hipLaunchKernelGGL(kernel_for(g, a.model, method, false), grid, block, 0, a.stream, c);
-      HIP_OK(hipGetLastError());
-    }
-  } else {
-    // BRDF_HIP_EXACT_POW=1: mark every fit for the exact kernel
-    HIP_OK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags), kNeedsExact, (size_t)a.S, a.stream));
-    hipLaunchKernelGGL(kernel_for(g, a.model, method, false), grid, block, 0, a.stream, c);
-    HIP_OK(hipGetLastError());
-  }
-  return 0;
+  // fits with a cosine <= 0 mark themselves: second launch on the exact path (Ward's prepared path has no domain restriction)
+  return launch_fast_then_exact(fast, a.model != MODEL_WARD, flags, (size_t)a.S, nullptr, a.stream, [&](bool fast_kernel, int *) {
+    hipLaunchKernelGGL(kernel_for(g, a.model, method, fast_kernel), dim3(a.S), dim3(g.threads), 0, a.stream, c);
+  });
 }
 }  // namespace
 
@@ -761,28 +704,14 @@ int batch_fit_launches(const BatchFitArgs &a, const Geometry &g, int *flags, int
 // after the other through the single-fit path (resident regime up to #CUs * 4096 samples, the launch chain beyond), each
 // using every CU.  The starting points travel to the host and the results back: synchronous on a.stream.
 namespace {
-int batch_of_large_fits(const BatchFitArgs &a) {
+int batch_of_large_fits(const BatchFitArgs &a, MethodSpec ms) {
   std::vector<double> p((size_t)a.S * kM), info((size_t)a.S * kInfoSz);
   std::vector<int> ret(a.S);
   HIP_OK(hipMemcpyAsync(p.data(), a.d_p, sizeof(double) * p.size(), hipMemcpyDeviceToHost, a.stream));
   HIP_OK(hipStreamSynchronize(a.stream));
   for (int s = 0; s < a.S; ++s) {
-    StreamFitArgs f;
-    f.method = (a.method == BRDF_METHOD_BC_DER) ? 1 : (a.method == BRDF_METHOD_DER ? 2 : a.method);
-    f.analytic = (a.method == BRDF_METHOD_BC_DER || a.method == BRDF_METHOD_DER) ? 1 : 0;
-    f.model = a.model;
-    f.d_angles = a.d_angles + (size_t)s * 3 * a.n;
-    f.d_x = a.d_x + (size_t)s * a.n;
-    f.n = a.n;
-    f.p = p.data() + (size_t)s * kM;
-    f.lb = a.lb;
-    f.ub = a.ub;
-    f.dscl = nullptr;
-    f.itmax = a.itmax;
-    f.opts = a.opts;
-    f.info = info.data() + (size_t)s * kInfoSz;
-    f.covar = nullptr;
-    f.stream = a.stream;
+    const StreamFitArgs f = stream_fit_args(ms, a.model, a.d_angles + (size_t)s * 3 * a.n, a.d_x + (size_t)s * a.n, a.n, p.data() + (size_t)s * kM,
+                                            a.lb, a.ub, nullptr, a.itmax, a.opts, info.data() + (size_t)s * kInfoSz, nullptr, a.stream);
     ret[s] = stream_fit_run(f);
   }
   HIP_OK(hipMemcpyAsync(a.d_p, p.data(), sizeof(double) * p.size(), hipMemcpyHostToDevice, a.stream));
@@ -794,7 +723,8 @@ int batch_of_large_fits(const BatchFitArgs &a) {
 }  // namespace
 
 int batch_fit_enqueue(const BatchFitArgs &a) {
-  if (a.model < 0 || a.model >= MODEL_COUNT || a.method < 0 || a.method > BRDF_METHOD_DER) {
+  MethodSpec ms;
+  if (a.model < 0 || a.model >= MODEL_COUNT || !method_spec(a.method, &ms)) {
     set_error("brdf_hip_fit_batch_dev(): unknown model %d / method %d", a.model, a.method);
     return kLmError;
   }
@@ -803,8 +733,8 @@ int batch_fit_enqueue(const BatchFitArgs &a) {
     return kLmError;
   }
   Geometry g;
-  if (!geometry_for(a.n, &g)) return batch_of_large_fits(a);  // n > 4096: one fit after the other, each spread over the chip
-  if ((a.method == 1 || a.method == BRDF_METHOD_BC_DER) && a.lb && a.ub)
+  if (!geometry_for(a.n, &g)) return batch_of_large_fits(a, ms);  // n > 4096: one fit after the other, each spread over the chip
+  if (ms.machine == kBcMachine && a.lb && a.ub)
     for (int i = 0; i < kM; ++i)
       if (a.lb[i] > a.ub[i]) {  // lmbc_core.c:451-454
         set_bad_input_error("dlevmar_bc_dif", 2, a.n, kM);
@@ -814,20 +744,13 @@ int batch_fit_enqueue(const BatchFitArgs &a) {
   int dev = 0;
   HIP_OK(hipGetDevice(&dev));
   BatchScratch &sc = g_scratch;
-  if (sc.device != dev || sc.cap < (size_t)a.S) {
-    if (sc.ptr) {
-      HIP_OK(hipDeviceSynchronize());  // a previous batch (any stream) may still use the old block
-      (void)hipFree(sc.ptr);
-      if (sc.last_use) (void)hipEventDestroy(sc.last_use);
-      sc = BatchScratch{};
-    }
-    HIP_OK(hipMalloc(&sc.ptr, sizeof(int) * ((size_t)a.S + 2)));
+  if (!sc.block.holds((size_t)a.S + 2, dev)) {
+    sc.release();  // (a previous batch, on any stream, may still use the old block)
+    HIP_OK(sc.block.ensure((size_t)a.S + 2, dev));
     HIP_OK(hipEventCreateWithFlags(&sc.last_use, hipEventDisableTiming));
-    sc.cap = (size_t)a.S;
-    sc.device = dev;
   }
   if (sc.in_use) HIP_OK(hipStreamWaitEvent(a.stream, sc.last_use, 0));
-  const int rc = batch_fit_launches(a, g, sc.ptr, sc.ptr + sc.cap);
+  const int rc = batch_fit_launches(a, ms, g, sc.block.ptr, sc.block.ptr + sc.fits());
   sc.in_use = true;  // (also after a failed enqueue: some launches may be in flight)
   HIP_OK(hipEventRecord(sc.last_use, a.stream));
   return rc;

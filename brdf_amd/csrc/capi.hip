@@ -18,21 +18,6 @@
 #include "fit_host.h"
 #include "fit_stats.h"
 
-namespace brdf {
-int generic_fit_run(int method, void (*func)(double *, double *, int, int, void *),
-                    void (*jacf)(double *, double *, int, int, void *), double *p, double *x, int m, int n, double *lb,
-                    double *ub, double *dscl, int itmax, double *opts, double *info, double *covar, void *adata);
-int model_eval_run(int model, const double *d_angles, int n, const double *p, double *d_hx, hipStream_t stream);
-int model_jac_run(int model, const double *d_angles, int n, const double *p, double *d_jac, hipStream_t stream);
-int chkjac_err_run(const double *fvec, const double *fjac, const double *fvecp, const double *p, int m, int n, double *err);
-int r2_run(const double *x, const double *hx, int n, double *r2);
-int generic_fit_run_f(int method, void (*func)(float *, float *, int, int, void *), void (*jacf)(float *, float *, int, int, void *),
-                      float *p, float *x, int m, int n, float *lb, float *ub, float *dscl, int itmax, float *opts, float *info,
-                      float *covar, void *adata);
-int chkjac_err_run_f(const float *fvec, const float *fjac, const float *fvecp, const float *p, int m, int n, float *err);
-int r2_run_f(const float *x, const float *hx, int n, float *r2);
-}
-
 using namespace brdf;
 
 namespace {
@@ -63,43 +48,21 @@ bool is_registered(model_func_t f) {
   return false;
 }
 
-// Grow-only device staging of the drop-in entry points (one per host thread): a dlevmar_* call with host pointers
-// uploads its planes and measurements here.  The first version hipMalloc'ed and hipFree'd two buffers per call -- at the
-// application's call site (brdfdata.cpp:1119: n = 16, once per pixel and colour channel) that pair cost more than the fit.
-struct HostStage {
-  double *d = nullptr;
-  size_t cap = 0;
-  int dev = -1;
-  // the block belongs to device `dev`: work queued THERE has to drain before it is freed, whatever device is current now
-  void release() {
-    if (!d) return;
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    if (cur != dev) (void)hipSetDevice(dev);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(d);
-    if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
-    d = nullptr;
-    cap = 0;
+// Grow-only device staging of the drop-in entry points (one per host thread, given back when the thread ends): a dlevmar_* call
+// with host pointers uploads its planes and measurements here.  The first version hipMalloc'ed and hipFree'd two buffers per call --
+// at the application's call site (brdfdata.cpp:1119: n = 16, once per pixel and colour channel) that pair cost more than the fit.
+thread_local DeviceBlock<double> g_stage;
+double *stage_get(size_t count) {
+  int cur = 0;
+  if (hipGetDevice(&cur) != hipSuccess) return nullptr;
+  if (g_stage.holds(count, cur)) return g_stage.ptr;
+  const size_t want = count + count / 2 + 1024;
+  if (g_stage.ensure(want, cur) != hipSuccess) {
+    set_error("hipMalloc(%zu doubles) failed", want);
+    return nullptr;
   }
-  ~HostStage() { release(); }  // a host thread that ends gives its staging block back
-  double *get(size_t count) {
-    int cur = 0;
-    if (hipGetDevice(&cur) != hipSuccess) return nullptr;
-    if (d && cur == dev && cap >= count) return d;
-    release();
-    const size_t want = count + count / 2 + 1024;
-    if (hipMalloc(&d, want * sizeof(double)) != hipSuccess) {
-      set_error("hipMalloc(%zu doubles) failed", want);
-      d = nullptr;
-      return nullptr;
-    }
-    cap = want;
-    dev = cur;
-    return d;
-  }
-};
-thread_local HostStage g_stage;
+  return g_stage.ptr;
+}
 
 // uploads the planes `modelInfo` reads (Blinn-Phong never reads plane 3, which the reference's per-surfel caller
 // allocates and fills incorrectly, brdfdata.cpp:1095, :1102) into d[0, 3n): adjacent planes travel in one copy
@@ -112,30 +75,22 @@ hipError_t upload_planes(double *d, const double *angles, int n, int model) {
 }
 
 // scoped device buffer
-struct DevBuf {
-  double *ptr = nullptr;
-  ~DevBuf() {
-    if (ptr) (void)hipFree(ptr);
-  }
-  int alloc(size_t count) {
-    hipError_t e = hipMalloc(&ptr, count * sizeof(double));
-    if (e != hipSuccess) {
-      set_error("hipMalloc(%zu doubles) failed: %s", count, hipGetErrorString(e));
-      ptr = nullptr;
-      return -1;
-    }
-    return 0;
-  }
-};
+using DevBuf = DeviceBlock<double>;
+int alloc_doubles(DevBuf &b, size_t count) {
+  const hipError_t e = b.ensure(count);
+  if (e == hipSuccess) return 0;
+  set_error("hipMalloc(%zu doubles) failed: %s", count, hipGetErrorString(e));
+  return -1;
+}
 
-int host_fit(int method, const char *who, model_func_t func, double *p, double *x, int m, int n, double *lb,
-             double *ub, double *dscl, int itmax, double *opts, double *info, double *covar, void *adata, int analytic = 0) {
+int host_fit(MethodSpec ms, const char *who, model_func_t func, double *p, double *x, int m, int n, double *lb,
+             double *ub, double *dscl, int itmax, double *opts, double *info, double *covar, void *adata) {
   if (!func) {
     set_error("%s(): func is NULL", who);
     return LM_ERROR;
   }
   if (!is_registered(func))  // arbitrary host callback: evaluated on the host, all n-sized algebra on the device
-    return generic_fit_run(method, func, nullptr, p, x, m, n, lb, ub, dscl, itmax, opts, info, covar, adata);
+    return generic_fit_run(ms.machine, func, nullptr, p, x, m, n, lb, ub, dscl, itmax, opts, info, covar, adata);
   if (m != kM) {
     set_error("%s(): the BRDF models have exactly 3 parameters (got m=%d)", who, m);
     return LM_ERROR;
@@ -158,7 +113,7 @@ int host_fit(int method, const char *who, model_func_t func, double *p, double *
               ed->modelInfo);
     return LM_ERROR;
   }
-  double *stage = g_stage.get(4 * (size_t)n);
+  double *stage = stage_get(4 * (size_t)n);
   if (!stage) return LM_ERROR;
   double *d_angles = stage, *d_x = stage + 3 * (size_t)n;
   hipError_t e = upload_planes(d_angles, ed->angles, n, ed->modelInfo);
@@ -168,25 +123,9 @@ int host_fit(int method, const char *who, model_func_t func, double *p, double *
     set_error("%s(): host->device copy failed: %s", who, hipGetErrorString(e));
     return LM_ERROR;
   }
-  StreamFitArgs a;
-  a.method = method;
-  a.analytic = analytic;
-  a.model = ed->modelInfo;
-  a.d_angles = d_angles;
-  a.d_x = d_x;
-  a.n = n;
-  a.p = p;
-  a.lb = lb;
-  a.ub = ub;
-  a.dscl = dscl;
-  a.itmax = itmax;
-  a.opts = opts;
-  a.info = info;
-  a.covar = covar;
-  a.stream = nullptr;
   // (the fit has finished when this returns: launches of the chain still queued behind it only read its `done` word,
   // never the staging buffer, so the next call may overwrite the buffer at once)
-  return stream_fit_run(a);
+  return stream_fit_run(stream_fit_args(ms, ed->modelInfo, d_angles, d_x, n, p, lb, ub, dscl, itmax, opts, info, covar, nullptr));
 }
 
 }  // namespace
@@ -269,14 +208,14 @@ extern "C" {
 
 int dlevmar_dif(void (*func)(double *, double *, int, int, void *), double *p, double *x, int m, int n, int itmax,
                 double *opts, double *info, double * /*work*/, double *covar, void *adata) {
-  return host_fit(BRDF_METHOD_DIF, "dlevmar_dif", func, p, x, m, n, nullptr, nullptr, nullptr, itmax, opts, info,
+  return host_fit({kDifMachine, false}, "dlevmar_dif", func, p, x, m, n, nullptr, nullptr, nullptr, itmax, opts, info,
                   covar, adata);
 }
 
 int dlevmar_bc_dif(void (*func)(double *, double *, int, int, void *), double *p, double *x, int m, int n,
                    double *lb, double *ub, double *dscl, int itmax, double *opts, double *info, double * /*work*/,
                    double *covar, void *adata) {
-  return host_fit(BRDF_METHOD_BC_DIF, "dlevmar_bc_dif", func, p, x, m, n, lb, ub, dscl, itmax, opts, info, covar,
+  return host_fit({kBcMachine, false}, "dlevmar_bc_dif", func, p, x, m, n, lb, ub, dscl, itmax, opts, info, covar,
                   adata);
 }
 
@@ -295,8 +234,8 @@ int dlevmar_der(void (*func)(double *, double *, int, int, void *), void (*jacf)
   Opts4 o4(opts);
   opts = o4.ptr;
   if (is_registered(func) && jacf == &BRDFJac_hip)  // a built-in model with its own analytic Jacobian: all on the device
-    return host_fit(2, "dlevmar_der", func, p, x, m, n, nullptr, nullptr, nullptr, itmax, opts, info, covar, adata, 1);
-  return generic_fit_run(2, func, jacf, p, x, m, n, nullptr, nullptr, nullptr, itmax, opts, info, covar, adata);
+    return host_fit({kDerMachine, true}, "dlevmar_der", func, p, x, m, n, nullptr, nullptr, nullptr, itmax, opts, info, covar, adata);
+  return generic_fit_run(kDerMachine, func, jacf, p, x, m, n, nullptr, nullptr, nullptr, itmax, opts, info, covar, adata);
 }
 
 int dlevmar_bc_der(void (*func)(double *, double *, int, int, void *), void (*jacf)(double *, double *, int, int, void *),
@@ -314,9 +253,8 @@ int dlevmar_bc_der(void (*func)(double *, double *, int, int, void *), void (*ja
   Opts4 o4(opts);
   opts = o4.ptr;
   if (is_registered(func) && jacf == &BRDFJac_hip)  // a built-in model with its own analytic Jacobian: all on the device
-    return host_fit(BRDF_METHOD_BC_DIF, "dlevmar_bc_der", func, p, x, m, n, lb, ub, dscl, itmax, opts, info, covar, adata,
-                    /*analytic=*/1);
-  return generic_fit_run(BRDF_METHOD_BC_DIF, func, jacf, p, x, m, n, lb, ub, dscl, itmax, opts, info, covar, adata);
+    return host_fit({kBcMachine, true}, "dlevmar_bc_der", func, p, x, m, n, lb, ub, dscl, itmax, opts, info, covar, adata);
+  return generic_fit_run(kBcMachine, func, jacf, p, x, m, n, lb, ub, dscl, itmax, opts, info, covar, adata);
 }
 
 /* scalar post-processing of the covariance the solvers return (misc_core.c:598-611); no n-sized work */
@@ -344,11 +282,11 @@ int sAx_eq_b_LU_noLapack(float *A, float *B, float *x, int m) { return lu_noLapa
  * order for n*m <= 65536.  (There is no registered-model shortcut: the BRDF application is double-only.) */
 int slevmar_dif(void (*func)(float *, float *, int, int, void *), float *p, float *x, int m, int n, int itmax, float *opts,
                 float *info, float * /*work*/, float *covar, void *adata) {
-  return generic_fit_run_f(0, func, nullptr, p, x, m, n, nullptr, nullptr, nullptr, itmax, opts, info, covar, adata);
+  return generic_fit_run_f(kDifMachine, func, nullptr, p, x, m, n, nullptr, nullptr, nullptr, itmax, opts, info, covar, adata);
 }
 int slevmar_bc_dif(void (*func)(float *, float *, int, int, void *), float *p, float *x, int m, int n, float *lb, float *ub,
                    float *dscl, int itmax, float *opts, float *info, float * /*work*/, float *covar, void *adata) {
-  return generic_fit_run_f(1, func, nullptr, p, x, m, n, lb, ub, dscl, itmax, opts, info, covar, adata);
+  return generic_fit_run_f(kBcMachine, func, nullptr, p, x, m, n, lb, ub, dscl, itmax, opts, info, covar, adata);
 }
 int slevmar_der(void (*func)(float *, float *, int, int, void *), void (*jacf)(float *, float *, int, int, void *), float *p, float *x,
                 int m, int n, int itmax, float *opts, float *info, float * /*work*/, float *covar, void *adata) {
@@ -360,7 +298,7 @@ int slevmar_der(void (*func)(float *, float *, int, int, void *), void (*jacf)(f
   float o5[5] = {0, 0, 0, 0, (float)LM_DIFF_DELTA};  // four documented elements (see Opts4)
   if (opts)
     for (int i = 0; i < 4; ++i) o5[i] = opts[i];
-  return generic_fit_run_f(2, func, jacf, p, x, m, n, nullptr, nullptr, nullptr, itmax, opts ? o5 : nullptr, info, covar, adata);
+  return generic_fit_run_f(kDerMachine, func, jacf, p, x, m, n, nullptr, nullptr, nullptr, itmax, opts ? o5 : nullptr, info, covar, adata);
 }
 int slevmar_bc_der(void (*func)(float *, float *, int, int, void *), void (*jacf)(float *, float *, int, int, void *), float *p,
                    float *x, int m, int n, float *lb, float *ub, float *dscl, int itmax, float *opts, float *info, float * /*work*/,
@@ -373,7 +311,7 @@ int slevmar_bc_der(void (*func)(float *, float *, int, int, void *), void (*jacf
   float o5[5] = {0, 0, 0, 0, (float)LM_DIFF_DELTA};
   if (opts)
     for (int i = 0; i < 4; ++i) o5[i] = opts[i];
-  return generic_fit_run_f(1, func, jacf, p, x, m, n, lb, ub, dscl, itmax, opts ? o5 : nullptr, info, covar, adata);
+  return generic_fit_run_f(kBcMachine, func, jacf, p, x, m, n, lb, ub, dscl, itmax, opts ? o5 : nullptr, info, covar, adata);
 }
 float slevmar_stddev(float *covar, int m, int i) { return (float)sqrt(covar[i * m + i]); }  /* misc_core.c:598-602 */
 float slevmar_corcoef(float *covar, int m, int i, int j) { return (float)(covar[i * m + j] / sqrt(covar[i * m + i] * covar[j * m + j])); }
@@ -438,7 +376,7 @@ void BRDFFunc_hip(double *p, double *hx, int m, int n, void *adata) {
     return;
   }
   if (ed->modelInfo < 0 || ed->modelInfo >= MODEL_COUNT) return;  // reference: hx left unwritten
-  double *stage = g_stage.get(4 * (size_t)n);
+  double *stage = stage_get(4 * (size_t)n);
   if (!stage) return;
   double *d_out = stage + 3 * (size_t)n;
   hipError_t e = upload_planes(stage, ed->angles, n, ed->modelInfo);
@@ -458,7 +396,7 @@ void BRDFJac_hip(double *p, double *jac, int m, int n, void *adata) {
     return;
   }
   if (ed->modelInfo < 0 || ed->modelInfo >= MODEL_COUNT) return;
-  double *stage = g_stage.get(6 * (size_t)n);
+  double *stage = stage_get(6 * (size_t)n);
   if (!stage) return;
   double *d_out = stage + 3 * (size_t)n;
   hipError_t e = upload_planes(stage, ed->angles, n, ed->modelInfo);
@@ -494,23 +432,9 @@ void dlevmar_chkjac(void (*func)(double *, double *, int, int, void *), void (*j
 int brdf_hip_fit_dev(int method, int model, const double *d_angles, const double *d_x, int n, double *p,
                      const double *lb, const double *ub, const double *dscl, int itmax, const double *opts,
                      double *info, double *covar, void *stream) {
-  StreamFitArgs a;
-  a.method = (method == BRDF_METHOD_BC_DER) ? 1 : (method == BRDF_METHOD_DER ? 2 : method);  // internal: 2 = DerMachine
-  a.analytic = (method == BRDF_METHOD_BC_DER || method == BRDF_METHOD_DER) ? 1 : 0;
-  a.model = model;
-  a.d_angles = d_angles;
-  a.d_x = d_x;
-  a.n = n;
-  a.p = p;
-  a.lb = lb;
-  a.ub = ub;
-  a.dscl = dscl;
-  a.itmax = itmax;
-  a.opts = opts;
-  a.info = info;
-  a.covar = covar;
-  a.stream = static_cast<hipStream_t>(stream);
-  return stream_fit_run(a);
+  MethodSpec ms;
+  (void)method_spec(method, &ms);  // (an unknown method: stream_fit_run's words)
+  return stream_fit_run(stream_fit_args(ms, model, d_angles, d_x, n, p, lb, ub, dscl, itmax, opts, info, covar, static_cast<hipStream_t>(stream)));
 }
 
 int brdf_hip_fit_channels_dev(int method, int model, const double *d_angles, const double *d_x, long long x_stride, int n, int channels,
@@ -520,7 +444,8 @@ int brdf_hip_fit_channels_dev(int method, int model, const double *d_angles, con
     set_error("brdf_hip_fit_channels_dev(): bad arguments");
     return LM_ERROR;
   }
-  if (method < 0 || method > 3 || model < 0 || model >= MODEL_COUNT) {
+  MethodSpec ms;
+  if (!method_spec(method, &ms) || model < 0 || model >= MODEL_COUNT) {
     set_error("brdf_hip_fit_channels_dev(): unknown method %d or model %d", method, model);
     return LM_ERROR;
   }
@@ -573,8 +498,8 @@ int brdf_hip_fit_batch(int method, int model, const double *angles, const double
   }
   const size_t sn = (size_t)S * n;
   DevBuf d_angles, d_x, d_p, d_info, d_ret;
-  if (d_angles.alloc(3 * sn) || d_x.alloc(sn) || d_p.alloc(3 * (size_t)S) || d_info.alloc(10 * (size_t)S) ||
-      d_ret.alloc(((size_t)S + 1) / 2 + 1))
+  if (alloc_doubles(d_angles, 3 * sn) || alloc_doubles(d_x, sn) || alloc_doubles(d_p, 3 * (size_t)S) || alloc_doubles(d_info, 10 * (size_t)S) ||
+      alloc_doubles(d_ret, ((size_t)S + 1) / 2 + 1))
     return LM_ERROR;
   hipError_t e = hipMemcpy(d_angles.ptr, angles, sizeof(double) * 3 * sn, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_x.ptr, x, sizeof(double) * sn, hipMemcpyHostToDevice);
@@ -642,8 +567,8 @@ int brdf_hip_fit_stats_batch(int method, int model, const double *angles, const 
   if (fit_stats_check(a, who) != 0) return LM_ERROR;
   const size_t sn = (size_t)S * n;
   DevBuf d_angles, d_x, d_p, d_covar, d_stats, d_rank;
-  if (d_angles.alloc(3 * sn) || d_x.alloc(sn) || d_p.alloc(3 * (size_t)S) || (covar && d_covar.alloc(9 * (size_t)S)) ||
-      (stats && d_stats.alloc(BRDF_STATS_SZ * (size_t)S)) || (rank && d_rank.alloc(((size_t)S + 1) / 2 + 1)))
+  if (alloc_doubles(d_angles, 3 * sn) || alloc_doubles(d_x, sn) || alloc_doubles(d_p, 3 * (size_t)S) || (covar && alloc_doubles(d_covar, 9 * (size_t)S)) ||
+      (stats && alloc_doubles(d_stats, BRDF_STATS_SZ * (size_t)S)) || (rank && alloc_doubles(d_rank, ((size_t)S + 1) / 2 + 1)))
     return LM_ERROR;
   hipError_t e = hipMemcpy(d_angles.ptr, angles, sizeof(double) * 3 * sn, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_x.ptr, x, sizeof(double) * sn, hipMemcpyHostToDevice);

@@ -18,9 +18,9 @@
 #include <cstdio>
 #include <vector>
 
-#include "batch_fit.h"
+#include "../../include/brdf_levmar.h"
+#include "fit_host.h"
 #include "fit_stats.h"
-#include "stream_fit.h"
 
 namespace brdf {
 
@@ -172,15 +172,7 @@ __global__ __launch_bounds__(kCT) void single_pack_kernel(const unsigned char *i
   }
 }
 
-struct DevBuf {
-  void *ptr = nullptr;
-  ~DevBuf() {
-    if (ptr) (void)hipFree(ptr);
-  }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&ptr, bytes ? bytes : 1); }
-  template <class T>
-  T *as() const { return static_cast<T *>(ptr); }
-};
+using DevBuf = DeviceBlock<char>;  // scoped: bytes
 
 #define CAP_OK(call)                                                                      \
   do {                                                                                    \
@@ -213,9 +205,9 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
   const long long npx = (long long)H * W;
   const int nb = (int)((npx + kCT - 1) / kCT);
   DevBuf counts, offsets, last;
-  CAP_OK(counts.alloc(sizeof(int) * nb));
-  CAP_OK(offsets.alloc(sizeof(long long) * nb));
-  CAP_OK(last.alloc(sizeof(long long) * nf));
+  CAP_OK(counts.ensure(sizeof(int) * nb));
+  CAP_OK(offsets.ensure(sizeof(long long) * nb));
+  CAP_OK(last.ensure(sizeof(long long) * nf));
   CAP_OK(hipMemsetAsync(last.ptr, 0, sizeof(long long) * nf, stream));
   hipLaunchKernelGGL(count_kernel, dim3(nb), dim3(kCT), 0, stream, d_pixel_map, H, W, nf, counts.as<int>());
   std::vector<int> h_counts(nb);
@@ -236,14 +228,14 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
   }
   CAP_OK(hipMemcpyAsync(offsets.ptr, h_off.data(), sizeof(long long) * nb, hipMemcpyHostToDevice, stream));
   DevBuf pixel_of, face_s, faces3, x, p, angles, ret, p0d, sums;
-  CAP_OK(pixel_of.alloc(sizeof(long long) * S));
-  CAP_OK(face_s.alloc(sizeof(int) * S));
-  CAP_OK(faces3.alloc(sizeof(int) * 3 * S));
-  CAP_OK(x.alloc(sizeof(double) * 3 * S * L));
-  CAP_OK(p.alloc(sizeof(double) * 9 * S));
-  CAP_OK(angles.alloc(sizeof(double) * 9 * S * L));
-  CAP_OK(ret.alloc(sizeof(int) * 3 * S));
-  CAP_OK(p0d.alloc(sizeof(double) * 3));
+  CAP_OK(pixel_of.ensure(sizeof(long long) * S));
+  CAP_OK(face_s.ensure(sizeof(int) * S));
+  CAP_OK(faces3.ensure(sizeof(int) * 3 * S));
+  CAP_OK(x.ensure(sizeof(double) * 3 * S * L));
+  CAP_OK(p.ensure(sizeof(double) * 9 * S));
+  CAP_OK(angles.ensure(sizeof(double) * 9 * S * L));
+  CAP_OK(ret.ensure(sizeof(int) * 3 * S));
+  CAP_OK(p0d.ensure(sizeof(double) * 3));
   CAP_OK(hipMemcpyAsync(p0d.ptr, p0, sizeof(double) * 3, hipMemcpyHostToDevice, stream));
   hipLaunchKernelGGL(compact_kernel, dim3(nb), dim3(kCT), 0, stream, d_pixel_map, H, W, nf, offsets.as<long long>(),
                      pixel_of.as<long long>(), face_s.as<int>(), last.as<long long>());
@@ -255,7 +247,7 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
   if (cosines_run(d_vertices, d_faces, d_normals, faces3.as<int>(), 3 * S, leds, L, view, rv_mode, angles.as<double>(), stream) != 0)
     return kLmError;
   BatchFitArgs a;
-  a.method = 1;  // dlevmar_bc_dif, brdfdata.cpp:1119
+  a.method = BRDF_METHOD_BC_DIF;  // brdfdata.cpp:1119
   a.model = model;
   a.d_angles = angles.as<double>();
   a.d_x = x.as<double>();
@@ -271,13 +263,13 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
   a.stream = stream;
   if (batch_fit_enqueue(a) != 0) return kLmError;
   const int sb = (int)((3 * S + kCT - 1) / kCT);
-  CAP_OK(sums.alloc(sizeof(double) * 3 * sb));
+  CAP_OK(sums.ensure(sizeof(double) * 3 * sb));
   hipLaunchKernelGGL(store_kernel, dim3(sb), dim3(kCT), 0, stream, p.as<double>(), face_s.as<int>(), last.as<long long>(), S,
                      d_brdf_surfaces, sums.as<double>());
   CAP_OK(hipGetLastError());
   DevBuf src_of_row;
   if (want_stats) {  // the staged angles / x / p are still in HBM: one pass over the stored fits
-    CAP_OK(src_of_row.alloc(sizeof(int) * 3 * (size_t)nf));
+    CAP_OK(src_of_row.ensure(sizeof(int) * 3 * (size_t)nf));
     hipLaunchKernelGGL(stats_rows_kernel, dim3((3 * nf + kCT - 1) / kCT), dim3(kCT), 0, stream, last.as<long long>(), nf, src_of_row.as<int>());
     CAP_OK(hipGetLastError());
     FitStatsArgs fs;
@@ -328,11 +320,11 @@ int capture_fit_single_run(int model, const unsigned char *d_images, int L, int 
   const long long npx = (long long)H * W;
   const int nb = (int)((npx + kCT - 1) / kCT), fb = (nf + kCT - 1) / kCT;
   DevBuf counts, offsets, last, fcounts, foffsets;
-  CAP_OK(counts.alloc(sizeof(int) * nb));
-  CAP_OK(offsets.alloc(sizeof(long long) * nb));
-  CAP_OK(last.alloc(sizeof(long long) * nf));
-  CAP_OK(fcounts.alloc(sizeof(int) * fb));
-  CAP_OK(foffsets.alloc(sizeof(long long) * fb));
+  CAP_OK(counts.ensure(sizeof(int) * nb));
+  CAP_OK(offsets.ensure(sizeof(long long) * nb));
+  CAP_OK(last.ensure(sizeof(long long) * nf));
+  CAP_OK(fcounts.ensure(sizeof(int) * fb));
+  CAP_OK(foffsets.ensure(sizeof(long long) * fb));
   CAP_OK(hipMemsetAsync(last.ptr, 0, sizeof(long long) * nf, stream));
   hipLaunchKernelGGL(count_kernel, dim3(nb), dim3(kCT), 0, stream, d_pixel_map, H, W, nf, counts.as<int>());
   std::vector<int> h_counts(nb);
@@ -351,8 +343,8 @@ int capture_fit_single_run(int model, const unsigned char *d_images, int L, int 
   }
   CAP_OK(hipMemcpyAsync(offsets.ptr, h_off.data(), sizeof(long long) * nb, hipMemcpyHostToDevice, stream));
   DevBuf pixel_of, face_s;
-  CAP_OK(pixel_of.alloc(sizeof(long long) * S));
-  CAP_OK(face_s.alloc(sizeof(int) * S));
+  CAP_OK(pixel_of.ensure(sizeof(long long) * S));
+  CAP_OK(face_s.ensure(sizeof(int) * S));
   hipLaunchKernelGGL(compact_kernel, dim3(nb), dim3(kCT), 0, stream, d_pixel_map, H, W, nf, offsets.as<long long>(),
                      pixel_of.as<long long>(), face_s.as<int>(), last.as<long long>());
   hipLaunchKernelGGL(face_count_kernel, dim3(fb), dim3(kCT), 0, stream, last.as<long long>(), nf, fcounts.as<int>());
@@ -373,11 +365,11 @@ int capture_fit_single_run(int model, const unsigned char *d_images, int L, int 
   }
   CAP_OK(hipMemcpyAsync(foffsets.ptr, h_fo.data(), sizeof(long long) * fb, hipMemcpyHostToDevice, stream));
   DevBuf face_list, pixel_list, angles_f, planes, x3;
-  CAP_OK(face_list.alloc(sizeof(int) * F));
-  CAP_OK(pixel_list.alloc(sizeof(long long) * F));
-  CAP_OK(angles_f.alloc(sizeof(double) * 3 * n));
-  CAP_OK(planes.alloc(sizeof(double) * 3 * n));
-  CAP_OK(x3.alloc(sizeof(double) * 3 * n));
+  CAP_OK(face_list.ensure(sizeof(int) * F));
+  CAP_OK(pixel_list.ensure(sizeof(long long) * F));
+  CAP_OK(angles_f.ensure(sizeof(double) * 3 * n));
+  CAP_OK(planes.ensure(sizeof(double) * 3 * n));
+  CAP_OK(x3.ensure(sizeof(double) * 3 * n));
   hipLaunchKernelGGL(face_compact_kernel, dim3(fb), dim3(kCT), 0, stream, last.as<long long>(), pixel_of.as<long long>(), nf,
                      foffsets.as<long long>(), face_list.as<int>(), pixel_list.as<long long>());
   CAP_OK(hipGetLastError());
@@ -393,7 +385,7 @@ int capture_fit_single_run(int model, const unsigned char *d_images, int L, int 
   double p3[9];
   for (int c = 0; c < 3; ++c)
     for (int k = 0; k < 3; ++k) p3[3 * c + k] = p0[k];
-  const int worst = channels_fit_run(/*method=*/1, model, planes.as<double>(), x3.as<double>(), n, (int)n, 3, p3, lb, ub, nullptr, itmax, opts,
+  const int worst = channels_fit_run(BRDF_METHOD_BC_DIF, model, planes.as<double>(), x3.as<double>(), n, (int)n, 3, p3, lb, ub, nullptr, itmax, opts,
                                      info, nullptr, stream);
   for (int k = 0; k < 9; ++k) single_brdf[k] = p3[k];
   CAP_OK(hipStreamSynchronize(stream));

@@ -16,7 +16,8 @@ ChannelsKernels (*const kKernels[MODEL_COUNT])() = {channels_kernels_0, channels
 std::atomic<int> g_fits_a_cu[MODEL_COUNT][2];  // kernel_fits_a_cu()'s answers
 
 struct ChannelsArgs {
-  int method, model;  // method: 1 dlevmar_bc_dif, 2 dlevmar_bc_der with the model's analytic Jacobian (BRDF_METHOD_*)
+  int model;
+  bool analytic;  // dlevmar_bc_der: the model's analytic Jacobian (the machine is always kBcMachine here)
   const double *d_angles;
   const double *d_x[kMaxChannels];
   int n, K;
@@ -52,7 +53,7 @@ int channels_attempt(const ChannelsKernels &kn, bool fast, const ChannelsArgs &a
   const int G = (int)std::min<long long>(ws.cus, std::max<long long>(1, ((long long)a.n + 1023) / 1024));  // (the single fit's grid)
   for (int c = 0; c < a.K; ++c) {  // the entry point's argument checks and warnings, per channel (the kernel starts its own machines)
     MachineUnion scratch;
-    if (start_fit_machine(scratch, 1, a.p + c * kM, a.n, a.lb, a.ub, a.dscl, a.itmax, a.opts, a.covar != nullptr, a.method == 2, fast) != 0)
+    if (start_fit_machine(scratch, kBcMachine, a.p + c * kM, a.n, a.lb, a.ub, a.dscl, a.itmax, a.opts, a.covar != nullptr, a.analytic, fast) != 0)
       return kLmError;
   }
   ws.clear_mailboxes();
@@ -67,8 +68,8 @@ int channels_attempt(const ChannelsKernels &kn, bool fast, const ChannelsArgs &a
   c.c1 = a.d_angles + a.n;
   c.c2 = a.d_angles + 2 * (size_t)a.n;
   for (int k = 0; k < kMaxChannels; ++k) c.x[k] = a.d_x[k < a.K ? k : 0];
-  c.ctl = reinterpret_cast<ResidentCtl *>(ws.d_block);
-  c.rows = reinterpret_cast<u64 *>(ws.d_block + CWorkspace::off_rows);
+  c.ctl = reinterpret_cast<ResidentCtl *>(ws.block.ptr);
+  c.rows = reinterpret_cast<u64 *>(ws.block.ptr + CWorkspace::off_rows);
   c.groups = c.rows + kMaxChannels * kRowsGranules;
   c.launch_id = ++ws.launches;  // nonzero, different for every launch on this workspace
   for (int k = 0; k < kMaxChannels; ++k)
@@ -85,9 +86,9 @@ int channels_attempt(const ChannelsKernels &kn, bool fast, const ChannelsArgs &a
   c.has_ub = a.ub != nullptr;
   c.has_dscl = a.dscl != nullptr;
   c.want_covar = a.covar != nullptr;
-  c.multi = pg_candidates();
-  c.analytic = a.method == 2 ? 1 : 0;
-  c.spec_jac = bc_spec_jac_enabled() ? 1 : 0;
+  c.multi = (int)switch_number(kSwPgMulti);
+  c.analytic = a.analytic ? 1 : 0;
+  c.spec_jac = switch_on(kSwSpecJac) ? 1 : 0;
   c.mbox = ws.d_mbox;
   c.n = a.n;
   c.K = a.K;
@@ -141,15 +142,9 @@ int channels_attempt(const ChannelsKernels &kn, bool fast, const ChannelsArgs &a
 
 // the fast model path first; the exact one where that is switched off, or met a cosine <= 0 (Ward has no exact path)
 int channels_run(const ChannelsKernels &kn, const ChannelsArgs &a, CWorkspace &ws, bool *unavailable) {
-  bool retry = false;
-  double keep[kMaxChannels * kM];
-  for (int i = 0; i < a.K * kM; ++i) keep[i] = a.p[i];
-  if (brdf_fast_path_enabled() || !kn.kernel[kExactPath]) {
-    const int ret = channels_attempt(kn, true, a, ws, &retry, unavailable);
-    if (!retry || *unavailable) return ret;
-    for (int i = 0; i < a.K * kM; ++i) a.p[i] = keep[i];
-  }
-  return kn.kernel[kExactPath] ? channels_attempt(kn, false, a, ws, &retry, unavailable) : kLmError;
+  static_assert(kMaxChannels * kM <= kRetryKeep, "with_exact_retry keeps every channel's starting point");
+  return with_exact_retry(a.p, a.K * kM, brdf_fast_path_enabled(), kn.kernel[kExactPath] != nullptr,
+                          [&](bool fast, bool *retry) { return channels_attempt(kn, fast, a, ws, retry, unavailable); });
 }
 
 }  // namespace
@@ -159,26 +154,20 @@ thread_local int g_channels_shared = 0;  // 1: the last call ran as ONE shared l
 int channels_last_shared() { return g_channels_shared; }
 FitStats channels_last_stats(int c) { return (c >= 0 && c < kMaxChannels) ? g_cws.stats[c] : FitStats{}; }
 
-// BRDF_HIP_CHANNELS=0: always one fit after the other
-static bool channels_enabled() {
-  const char *e = getenv("BRDF_HIP_CHANNELS");
-  return !(e && e[0] == '0');
-}
-
 int channels_fit_run(int method, int model, const double *d_angles, const double *d_x, long long x_stride, int n, int K, double *p,
                      const double *lb, const double *ub, const double *dscl, int itmax, const double *opts, double *info, double *covar,
                      hipStream_t stream) {
   g_channels_shared = 0;
-  const char *res = getenv("BRDF_HIP_RESIDENT");
-  const bool resident_ok = !(res && res[0] == '0');
+  MethodSpec ms;
+  (void)method_spec(method, &ms);  // (the entry point has refused anything else)
   int dev = 0;
   // the shared launch: box-constrained entry points, up to three channels, a fit that fits the chip
-  if (channels_enabled() && resident_ok && (method == 1 || method == 2) && K >= 2 && K <= kMaxChannels && hipGetDevice(&dev) == hipSuccess &&
+  if (switch_on(kSwChannels) && switch_on(kSwResident) && ms.machine == kBcMachine && K >= 2 && K <= kMaxChannels && hipGetDevice(&dev) == hipSuccess &&
       g_cws.ensure(dev) == 0 && (long long)n <= (long long)g_cws.cus * kRTile && g_cws.cus <= kRowStride) {
     CWorkspace &ws = g_cws;
     if (!ws.step_aside()) {  // (stepping aside after an aborted launch)
       ChannelsArgs a;
-      a.method = method;
+      a.analytic = ms.analytic;
       a.model = model;
       a.d_angles = d_angles;
       for (int c = 0; c < kMaxChannels; ++c) a.d_x[c] = d_x + (size_t)(c < K ? c : 0) * x_stride;
@@ -205,22 +194,8 @@ int channels_fit_run(int method, int model, const double *d_angles, const double
   }
   int worst = 0;
   for (int c = 0; c < K; ++c) {  // one fit after the other: the single-fit regimes (resident launch or launch chain)
-    StreamFitArgs a;
-    a.method = (method == 2) ? 1 : (method == 3 ? 2 : method);
-    a.model = model;
-    a.analytic = (method == 2 || method == 3) ? 1 : 0;
-    a.d_angles = d_angles;
-    a.d_x = d_x + (size_t)c * x_stride;
-    a.n = n;
-    a.p = p + c * kM;
-    a.lb = lb;
-    a.ub = ub;
-    a.dscl = dscl;
-    a.itmax = itmax;
-    a.opts = opts;
-    a.info = info ? info + c * kInfoSz : nullptr;
-    a.covar = covar ? covar + c * kM * kM : nullptr;
-    a.stream = stream;
+    const StreamFitArgs a = stream_fit_args(ms, model, d_angles, d_x + (size_t)c * x_stride, n, p + c * kM, lb, ub, dscl, itmax, opts,
+                                            info ? info + c * kInfoSz : nullptr, covar ? covar + c * kM * kM : nullptr, stream);
     const int r = stream_fit_run(a);
     if (c < kMaxChannels) g_cws.stats[c] = stream_fit_last_stats();
     if (r < 0) worst = kLmError;

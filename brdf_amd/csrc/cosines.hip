@@ -16,9 +16,8 @@
 // HBM-bound: per surfel 4 B (index) + 12 B (face) + 72 B (3 vertices, gathered) + 24 B (normal) in, 3 * L * 8 B out
 // (L = 16: 384 B), i.e. 496 B of algorithmic traffic per surfel.
 #include <cstdio>
-#include <cstdlib>
 
-#include "stream_fit.h"
+#include "fit_host.h"
 
 namespace brdf {
 
@@ -213,8 +212,7 @@ int cosines_run(const double *d_vertices, const int *d_faces, const double *d_no
   const long long per_block = 256 / L;  // whole surfels per workgroup and trip
   long long blocks = (S + per_block - 1) / per_block;
   if (blocks > 256 * 64) blocks = 256 * 64;  // grid-stride beyond 64 workgroups per CU
-  static const bool rows_off = [] { const char *e = getenv("BRDF_HIP_COSINES_ROWS"); return e && e[0] == '0'; }();
-  if (L == 16 && !rows_off)
+  if (L == 16 && switch_on(kSwCosinesRows))
     hipLaunchKernelGGL(cosines_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
   else
     hipLaunchKernelGGL(cosines_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);

@@ -1,11 +1,48 @@
-// fit_host.h -- the host half that the single-fit regimes share: the launch chain (stream_fit.hip), the resident launch
-// (resident_fit.hip) and channels sharing a launch (channels_fit.hip).  Host code only (fit_host.hip).
+// fit_host.h -- the host layer every regime shares (fit_host.hip): the C ABI's method codes, the environment switches
+// (fit_switches.h), the library's error text, memory that belongs to a device, the fast-then-exact launch protocol, and the host
+// half of the resident regimes (resident_fit.hip, channels_fit.hip).  Host code only.
 #pragma once
+
+#include "../../include/brdf_levmar.h"
+#include "fit_switches.h"
+
+namespace brdf {
+
+// ---- method codes ---------------------------------------------------------------------------------------------------------
+// Two numberings meet on the host.  The C ABI's BRDF_METHOD_{DIF, BC_DIF, BC_DER, DER} (0..3, include/brdf_levmar.h) names an
+// entry point; the kernels are instantiated per state machine, and take where the Jacobian rows come from as a run-time flag.
+enum Machine { kDifMachine = 0, kBcMachine = 1, kDerMachine = 2 };
+struct MethodSpec {
+  int machine;    // Machine: StreamFitArgs::method, the METHOD index of every kernel table
+  bool analytic;  // dlevmar_bc_der / dlevmar_der: the model's analytic Jacobian instead of finite differences
+};
+// false for anything outside 0..3; *out is then {abi_method, false}, for the callers whose own check words the error
+inline bool method_spec(int abi_method, MethodSpec *out) {
+  switch (abi_method) {
+  case BRDF_METHOD_DIF: *out = {kDifMachine, false}; return true;
+  case BRDF_METHOD_BC_DIF: *out = {kBcMachine, false}; return true;
+  case BRDF_METHOD_BC_DER: *out = {kBcMachine, true}; return true;
+  case BRDF_METHOD_DER: *out = {kDerMachine, true}; return true;
+  }
+  *out = {abi_method, false};
+  return false;
+}
+
+}  // namespace brdf
+
+#ifdef __HIPCC__  // the rest needs the HIP runtime (tests/cpp/fit_switches_harness.cpp reads the part above with a host compiler)
 
 #include <atomic>
 #include <cstring>
 
+#include "batch_fit.h"
 #include "stream_fit.h"
+
+namespace brdf {
+// the calling thread's last error text (brdf_hip_last_error); set_error also prints it to stderr
+void set_error(const char *fmt, ...);
+const char *get_error();
+}  // namespace brdf
 
 #define HIP_OK(call)                                                                  \
   do {                                                                                \
@@ -18,14 +55,131 @@
 
 namespace brdf {
 
+static_assert(kSwitchMaxCand == kMaxCand, "fit_switches.h clamps the candidate switches to lm_machine.h's kMaxCand");
+inline bool brdf_fast_path_enabled() { return !switch_on(kSwExactPow); }
+
+inline StreamFitArgs stream_fit_args(MethodSpec ms, int model, const double *d_angles, const double *d_x, int n, double *p, const double *lb,
+                                     const double *ub, const double *dscl, int itmax, const double *opts, double *info, double *covar,
+                                     hipStream_t stream) {
+  StreamFitArgs a;
+  a.method = ms.machine;
+  a.model = model;
+  a.analytic = ms.analytic ? 1 : 0;
+  a.d_angles = d_angles;
+  a.d_x = d_x;
+  a.n = n;
+  a.p = p;
+  a.lb = lb;
+  a.ub = ub;
+  a.dscl = dscl;
+  a.itmax = itmax;
+  a.opts = opts;
+  a.info = info;
+  a.covar = covar;
+  a.stream = stream;
+  return a;
+}
+
+// ---- memory that belongs to a device --------------------------------------------------------------------------------------
+// makes `dev` the current device for a scope (dev < 0: leaves it alone)
+struct DeviceScope {
+  int prev = -1;
+  bool switched = false;
+  explicit DeviceScope(int dev) {
+    if (dev >= 0 && hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
+  }
+  ~DeviceScope() {
+    if (switched) (void)hipSetDevice(prev);
+  }
+  DeviceScope(const DeviceScope &) = delete;
+  DeviceScope &operator=(const DeviceScope &) = delete;
+};
+
+// A grow-only block of `cap` T on device `device`.  It is given back on THAT device, whatever device is current then, after the
+// work queued there has drained (a launch on any stream may still use it).
+template <class T>
+struct DeviceBlock {
+  T *ptr = nullptr;
+  size_t cap = 0;
+  int device = -1;
+  DeviceBlock() = default;
+  DeviceBlock(const DeviceBlock &) = delete;
+  DeviceBlock &operator=(const DeviceBlock &) = delete;
+  ~DeviceBlock() { release(); }
+  bool holds(size_t count, int dev) const { return ptr && device == dev && cap >= count; }
+  // at least `count` elements on `dev`, which is the current device; what the block held before is lost when it has to move or grow
+  hipError_t ensure(size_t count, int dev) {
+    if (holds(count, dev)) return hipSuccess;
+    release();
+    const hipError_t e = hipMalloc(&ptr, (count ? count : 1) * sizeof(T));
+    if (e != hipSuccess) {
+      ptr = nullptr;
+      return e;
+    }
+    cap = count;
+    device = dev;
+    return hipSuccess;
+  }
+  hipError_t ensure(size_t count) {
+    int dev = 0;
+    const hipError_t e = hipGetDevice(&dev);
+    return e != hipSuccess ? e : ensure(count, dev);
+  }
+  void release() {
+    if (!ptr) return;
+    DeviceScope on(device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(ptr);
+    ptr = nullptr;
+    cap = 0;
+    device = -1;
+  }
+  template <class U>
+  U *as() const { return reinterpret_cast<U *>(ptr); }
+};
+
+// ---- fast, then exact -----------------------------------------------------------------------------------------------------
+// Batched: launch(true, queue) enqueues the prepared-sample kernel, launch(false, queue + 1) its exact twin over the fits that
+// marked themselves kNeedsExact (a cosine <= 0).  fast == false (BRDF_HIP_EXACT_POW=1): every fit is marked and only the exact
+// kernel runs.  flags [S]; queue: the kernel's work-queue word, one per launch (null: the kernel has none); Ward has no twin.
+template <class Launch>
+int launch_fast_then_exact(bool fast, bool has_exact_twin, int *flags, size_t S, int *queue, hipStream_t stream, Launch launch) {
+  if (!fast) HIP_OK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flags), kNeedsExact, S, stream));
+  launch(fast, queue);
+  HIP_OK(hipGetLastError());
+  if (fast && has_exact_twin) {
+    launch(false, queue ? queue + 1 : nullptr);
+    HIP_OK(hipGetLastError());
+  }
+  return 0;
+}
+
+// Single fit: attempt(fast, &retry_exact) runs one fit from p[0, count) and sets retry_exact when the fast path met a cosine <= 0
+// and its result is to be discarded; the exact attempt then starts from the same p.  try_fast == false: the exact path only,
+// where there is one.  (start_fit_machine keeps the starting point's warning from being printed by both attempts.)
+constexpr int kRetryKeep = 9;  // three channels' parameters
+template <class Attempt>
+int with_exact_retry(double *p, int count, bool try_fast, bool has_exact, Attempt attempt) {
+  bool retry = false;
+  double keep[kRetryKeep];
+  for (int i = 0; i < count; ++i) keep[i] = p[i];
+  if (try_fast || !has_exact) {
+    const int ret = attempt(true, &retry);
+    if (!retry) return ret;
+    for (int i = 0; i < count; ++i) p[i] = keep[i];
+  }
+  return has_exact ? attempt(false, &retry) : kLmError;
+}
+
+// ---- single fits ----------------------------------------------------------------------------------------------------------
 // levmar's words for the arguments a machine refused (Cold::bad_input: 1 n < m, lm_core.c:502-505 / lmbc_core.c:440-443; 2 a lower
 // bound above the upper one, lmbc_core.c:451-454; 3 a scaling constant <= 0, lmbc_core.c:456-461) and its warning about a
 // starting point outside the box (lmbc_core.c:516-520).  `who`: the entry point's name as the text shows it
 void set_bad_input_error(const char *who, int bad_input, int n, int m);
 void warn_start_projected(int i, double from, double to);
 
-// Starts the machine of `method` (0 dlevmar_dif, 1 dlevmar_bc_dif / bc_der, 2 dlevmar_der) in `m`.  The launch chain passes the
-// machine it uploads; the resident regimes a scratch one (their kernels start their own) for what this function does with it:
+// Starts the machine of `method` (a Machine) in `m`.  The launch chain passes the machine it uploads; the resident regimes a
+// scratch one (their kernels start their own) for what this function does with it:
 // refused arguments become the error text and kLmError, a projected starting point is warned about -- unless this is the exact
 // re-run of a fit the fast path has already warned about (`fast`: the attempt is on the fast model path).  Otherwise 0.
 int start_fit_machine(MachineUnion &m, int method, const double *p, int n, const double *lb, const double *ub, const double *dscl, int itmax,
@@ -36,8 +190,7 @@ int start_fit_machine(MachineUnion &m, int method, const double *p, int n, const
 void mailbox_to_caller(const Mailbox &mb, double *p, double *info, double *covar, FitStats *stats);
 
 // ---- the resident regimes -------------------------------------------------------------------------------------------------
-// the exchange's knobs: BRDF_HIP_RESIDENT_REPLICAS (1..max_replicas copies of the group rows), _SPIN_MS (budget of one wait, in
-// s_memrealtime ticks) and _SABOTAGE (tests only: the epoch at which the last workgroup withholds its row; -1 = never)
+// the exchange's knobs: BRDF_HIP_RESIDENT_REPLICAS, _SPIN_MS (here in s_memrealtime ticks) and _SABOTAGE (fit_switches.h)
 struct ExchangeKnobs {
   int replicas;
   long long spin_ticks;
@@ -49,12 +202,48 @@ ExchangeKnobs exchange_knobs(int max_replicas, long long default_spin_ticks);
 // kernel's answer, 0 = not asked yet (atomic: host threads on several devices get here at once)
 bool kernel_fits_a_cu(const void *kernel, int threads, std::atomic<int> &cached);
 
+// brdf_hip_set_launch_timing(): an event pair per host thread, created on first use on the current device
+struct LaunchTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  int device = -1;  // the events belong to the device they were created on
+  bool armed = false;
+  void drop() {
+    DeviceScope on(device);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    e0 = e1 = nullptr;
+  }
+  ~LaunchTimer() { drop(); }
+  void before(hipStream_t s) {
+    armed = false;
+    if (!launch_timing_enabled()) return;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) return;
+    if (dev != device) {
+      drop();
+      device = dev;
+    }
+    if (!e0 && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) {
+      drop();
+      return;
+    }
+    armed = hipEventRecord(e0, s) == hipSuccess;
+  }
+  void after(hipStream_t s) {
+    if (armed) armed = hipEventRecord(e1, s) == hipSuccess;
+  }
+  double elapsed_us() {  // after the launch is known to have finished
+    float ms = 0.0f;
+    if (!armed || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) return -1.0;
+    return 1e3 * (double)ms;
+  }
+};
+
 // What a host thread keeps per device for its resident launches: the device block (control words, exchange tables; zeroed),
 // the pinned mailboxes the kernels report to, the launch's event pair and the stepping aside after a launch that did not run.
 struct ResidentWorkspace {
   int device = -1, cus = 0;  // device < 0: not ready
-  char *d_block = nullptr;
-  size_t block_bytes = 0;
+  DeviceBlock<char> block;
   Mailbox *h_mbox = nullptr, *d_mbox = nullptr;  // [n_mbox]
   int n_mbox = 0;
   LaunchTimer timer;
@@ -67,7 +256,7 @@ struct ResidentWorkspace {
   bool ready(int dev) const { return device == dev; }
   int ensure(int dev, size_t bytes, int mailboxes);  // not ready after any failure
   int allocate(size_t bytes, int mailboxes);         // (ensure()'s: the blocks, on `device`)
-  void release();                                    // on the workspace's device, whatever device is current
+  void release();
   int zero_tables(hipStream_t stream);               // start over from zeroed control words and tables: the caller restarts its tags
   bool step_aside() {
     if (skip <= 0) return false;
@@ -83,4 +272,19 @@ struct ResidentWorkspace {
   int wait_for_mailboxes(int K, hipStream_t stream, bool *done);
 };
 
+// ---- host callbacks and small helpers (generic_fit.hip) -------------------------------------------------------------------
+// method: a Machine; jacf null: finite differences
+int generic_fit_run(int method, void (*func)(double *, double *, int, int, void *), void (*jacf)(double *, double *, int, int, void *),
+                    double *p, double *x, int m, int n, double *lb, double *ub, double *dscl, int itmax, double *opts, double *info,
+                    double *covar, void *adata);
+int generic_fit_run_f(int method, void (*func)(float *, float *, int, int, void *), void (*jacf)(float *, float *, int, int, void *),
+                      float *p, float *x, int m, int n, float *lb, float *ub, float *dscl, int itmax, float *opts, float *info,
+                      float *covar, void *adata);
+int chkjac_err_run(const double *fvec, const double *fjac, const double *fvecp, const double *p, int m, int n, double *err);
+int chkjac_err_run_f(const float *fvec, const float *fjac, const float *fvecp, const float *p, int m, int n, float *err);
+int r2_run(const double *x, const double *hx, int n, double *r2);
+int r2_run_f(const float *x, const float *hx, int n, float *r2);
+
 }  // namespace brdf
+
+#endif  // __HIPCC__

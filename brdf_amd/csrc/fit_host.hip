@@ -1,11 +1,21 @@
-// fit_host.hip -- the host half that the single-fit regimes share (see fit_host.h).
+// fit_host.hip -- the host layer every regime shares (see fit_host.h).
 #include <algorithm>
+#include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
 
 #include "fit_host.h"
 
 namespace brdf {
+
+static thread_local char g_err[512] = "";
+void set_error(const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof g_err, fmt, ap);
+  va_end(ap);
+  fprintf(stderr, "libbrdf_hip: %s\n", g_err);
+}
+const char *get_error() { return g_err; }
 
 void set_bad_input_error(const char *who, int bad_input, int n, int m) {
   switch (bad_input) {
@@ -21,20 +31,20 @@ void warn_start_projected(int i, double from, double to) {
 
 int start_fit_machine(MachineUnion &m, int method, const double *p, int n, const double *lb, const double *ub, const double *dscl, int itmax,
                       const double *opts, bool want_covar, bool analytic, bool fast) {
-  if (method == 0) {
-    m.dif.start(p, n, itmax, opts, want_covar, /*speculative=*/1, dif_chain_candidates());
+  if (method == kDifMachine) {
+    m.dif.start(p, n, itmax, opts, want_covar, /*speculative=*/1, (int)switch_number(kSwDifChain));
     if (m.dif.h.req.kind != RQ_DONE) return 0;
     set_bad_input_error("dlevmar_dif", 1, n, kM);
     return kLmError;
   }
-  if (method == 2) {
+  if (method == kDerMachine) {
     m.der.start(p, n, itmax, opts, want_covar);
     if (m.der.h.req.kind != RQ_DONE) return 0;
     set_bad_input_error("dlevmar_der", 1, n, kM);
     return kLmError;
   }
   BcMachine<kM> &bc = m.bc;
-  bc.start(p, n, lb, ub, dscl, itmax, opts, want_covar, pg_candidates(), bc_spec_jac_enabled() ? 1 : 0);
+  bc.start(p, n, lb, ub, dscl, itmax, opts, want_covar, (int)switch_number(kSwPgMulti), switch_on(kSwSpecJac) ? 1 : 0);
   bc.c.analytic_jac = analytic ? 1 : 0;
   if (bc.h.req.kind == RQ_DONE) {
     set_bad_input_error("dlevmar_bc_dif", bc.c.bad_input, n, kM);
@@ -60,11 +70,8 @@ void mailbox_to_caller(const Mailbox &mb, double *p, double *info, double *covar
 }
 
 ExchangeKnobs exchange_knobs(int max_replicas, long long default_spin_ticks) {
-  ExchangeKnobs k{max_replicas, default_spin_ticks, -1};
-  if (const char *e = getenv("BRDF_HIP_RESIDENT_REPLICAS")) k.replicas = std::min(max_replicas, std::max(1, atoi(e)));
-  if (const char *e = getenv("BRDF_HIP_RESIDENT_SPIN_MS")) k.spin_ticks = std::max(1LL, atoll(e)) * 100000LL;
-  if (const char *e = getenv("BRDF_HIP_RESIDENT_SABOTAGE")) k.sabotage_epoch = atoi(e);  // tests only: forces the fallback
-  return k;
+  return {(int)switch_number(kSwResidentReplicas, max_replicas, 1, max_replicas), resident_spin_ticks(default_spin_ticks),
+          (int)switch_number(kSwResidentSabotage)};
 }
 
 bool kernel_fits_a_cu(const void *kernel, int threads, std::atomic<int> &cached) {
@@ -78,18 +85,13 @@ bool kernel_fits_a_cu(const void *kernel, int threads, std::atomic<int> &cached)
   return v > 1;
 }
 
-// the blocks belong to `device`: drain and free them THERE, whatever device is current now
+// the blocks belong to `device`: they are given back THERE, whatever device is current now
 void ResidentWorkspace::release() {
-  if (d_block || h_mbox) {
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    if (device >= 0 && cur != device) (void)hipSetDevice(device);
-    (void)hipDeviceSynchronize();
-    if (d_block) (void)hipFree(d_block);
-    if (h_mbox) (void)hipHostFree(h_mbox);
-    if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
+  block.release();
+  if (h_mbox) {
+    DeviceScope on(device);
+    (void)hipHostFree(h_mbox);
   }
-  d_block = nullptr;
   h_mbox = d_mbox = nullptr;
   device = -1;
 }
@@ -98,11 +100,10 @@ int ResidentWorkspace::allocate(size_t bytes, int mailboxes) {
   hipDeviceProp_t prop;
   HIP_OK(hipGetDeviceProperties(&prop, device));
   cus = prop.multiProcessorCount;
-  HIP_OK(hipMalloc(&d_block, bytes));
-  HIP_OK(hipMemset(d_block, 0, bytes));
+  HIP_OK(block.ensure(bytes, device));
+  HIP_OK(hipMemset(block.ptr, 0, bytes));
   HIP_OK(hipHostMalloc(&h_mbox, sizeof(Mailbox) * (size_t)mailboxes, hipHostMallocMapped | hipHostMallocCoherent));
   HIP_OK(hipHostGetDevicePointer((void **)&d_mbox, h_mbox, 0));
-  block_bytes = bytes;
   n_mbox = mailboxes;
   return 0;
 }
@@ -117,14 +118,14 @@ int ResidentWorkspace::ensure(int dev, size_t bytes, int mailboxes) {
 }
 
 int ResidentWorkspace::zero_tables(hipStream_t stream) {
-  HIP_OK(hipMemsetAsync(d_block, 0, block_bytes, stream));
+  HIP_OK(hipMemsetAsync(block.ptr, 0, block.cap, stream));
   return 0;
 }
 
 void ResidentWorkspace::launch_unavailable() {
   backoff = std::min(1024, std::max(8, backoff * 2));
   skip = backoff;
-  if (const char *e = getenv("BRDF_HIP_RESIDENT_BACKOFF")) skip = std::max(0, atoi(e));
+  if (const long long fits = switch_number(kSwResidentBackoff); fits >= 0) skip = (int)fits;
 }
 
 int ResidentWorkspace::wait_for_mailboxes(int K, hipStream_t stream, bool *done) {

@@ -27,11 +27,10 @@
 // In the first three the per-fit sums are parked in LDS and the first lanes of the workgroup finish one fit each, so the
 // serial 3 x 3 LU runs in a few dense wavefronts instead of one lane of every wavefront.
 #include <cstdio>
-#include <cstdlib>
 
 #include "../../include/brdf_levmar.h"
 #include "fit_stats.h"
-#include "stream_fit.h"
+#include "fit_host.h"
 
 namespace brdf {
 
@@ -374,10 +373,7 @@ struct PartialK {
 // BRDF_HIP_STATS_FAST=1: the A/B variant DESIGN.md section 2 measures (the pass is bound by fp64 issue, and pow is most of it).  It is
 // NOT the default and has no exact fallback: exp(n log c) is off pow(c, n) by up to |n log c| ulp of the specular term, which the
 // statistics' parity bound (4 ulp of a model value) does not cover, and a cosine <= 0 turns the fit's sums into NaN (rank 0).
-bool stats_fast_path() {
-  const char *e = getenv("BRDF_HIP_STATS_FAST");
-  return e && e[0] == '1';
-}
+bool stats_fast_path() { return switch_on(kSwStatsFast); }
 
 #define STATS_OK(call)                                                        \
   do {                                                                        \
@@ -391,7 +387,8 @@ bool stats_fast_path() {
 }  // namespace
 
 int fit_stats_check(const FitStatsArgs &a, const char *who) {
-  if (a.model < 0 || a.model >= MODEL_COUNT || a.method < 0 || a.method > BRDF_METHOD_DER) {
+  MethodSpec ms;
+  if (a.model < 0 || a.model >= MODEL_COUNT || !method_spec(a.method, &ms)) {
     set_error("%s(): unknown model %d / method %d", who, a.model, a.method);
     return kLmError;
   }
@@ -428,7 +425,9 @@ int fit_stats_enqueue(const FitStatsArgs &a, const char *who) {
   const double d4 = a.opts ? a.opts[4] : LM_DIFF_DELTA;
   c.delta = d4 < 0.0 ? -d4 : d4;
   const bool fast = stats_fast_path();
-  const int jac = (a.method == BRDF_METHOD_BC_DER || a.method == BRDF_METHOD_DER) ? JAC_ANALYTIC : (d4 < 0.0 ? JAC_CENTRAL : JAC_FORWARD);
+  MethodSpec ms;
+  (void)method_spec(a.method, &ms);
+  const int jac = ms.analytic ? JAC_ANALYTIC : (d4 < 0.0 ? JAC_CENTRAL : JAC_FORWARD);
   if (c.rows <= 0) return 0;
   (void)hipGetLastError();
   if (a.n <= 16) {

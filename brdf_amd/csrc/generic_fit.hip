@@ -227,15 +227,6 @@ typedef user_jacf_of<double> user_jacf_t;
 
 namespace {
 
-template <class Real>
-struct GenBuffers {
-  Real *d = nullptr;
-  size_t cap = 0;
-  ~GenBuffers() {
-    if (d) (void)hipFree(d);
-  }
-};
-
 template <int M, int METHOD, class Real>
 int generic_run(user_func_of<Real> func, user_jacf_of<Real> jacf, Real *p, Real *x, int n, Real *lb, Real *ub, Real *dscl, int itmax,
                 Real *opts, Real *info, Real *covar, void *adata) {
@@ -264,9 +255,9 @@ int generic_run(user_func_of<Real> func, user_jacf_of<Real> jacf, Real *p, Real 
 
   // device buffers: x | hx | wrk | aux (2M planes) | jac (n*M) | out
   const size_t need = (size_t)n * (3 + 2 * M + M) + kGenSums;
-  GenBuffers<Real> buf;
-  HIP_OK(hipMalloc(&buf.d, need * sizeof(Real)));
-  Real *d_x = buf.d, *d_hx = d_x + n, *d_wrk = d_hx + n, *d_aux = d_wrk + n, *d_jac = d_aux + (size_t)2 * M * n,
+  DeviceBlock<Real> buf;
+  HIP_OK(buf.ensure(need));
+  Real *d_x = buf.ptr, *d_hx = d_x + n, *d_wrk = d_hx + n, *d_aux = d_wrk + n, *d_jac = d_aux + (size_t)2 * M * n,
          *d_out = d_jac + (size_t)n * M;
   std::vector<Real> host_aux((size_t)2 * M * n);
   if (x) {
@@ -464,9 +455,10 @@ __global__ __launch_bounds__(256) void chkjac_kernel(const Real *__restrict__ fv
 template <class Real>
 int chkjac_err_run_t(const Real *fvec, const Real *fjac, const Real *fvecp, const Real *p, int m, int n, Real *err) {
   (void)hipGetLastError();
-  Real *d = nullptr;
+  DeviceBlock<Real> buf;
   const size_t total = (size_t)n * (m + 3) + m;
-  if (hipMalloc(&d, total * sizeof(Real)) != hipSuccess) {
+  Real *const d = buf.ensure(total) == hipSuccess ? buf.ptr : nullptr;
+  if (!d) {
     set_error("dlevmar_chkjac(): hipMalloc failed");
     return kLmError;
   }
@@ -487,7 +479,6 @@ int chkjac_err_run_t(const Real *fvec, const Real *fjac, const Real *fvecp, cons
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(err, d_err, sizeof(Real) * n, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
   if (e != hipSuccess) {
     set_error("dlevmar_chkjac(): %s", hipGetErrorString(e));
     return kLmError;
@@ -548,8 +539,9 @@ __global__ __launch_bounds__(256) void r2_kernel(const Real *__restrict__ x, con
 template <class Real>
 int r2_run_t(const Real *x, const Real *hx, int n, Real *r2) {
   (void)hipGetLastError();
-  Real *d = nullptr;
-  if (hipMalloc(&d, (2 * (size_t)n + 1) * sizeof(Real)) != hipSuccess) {
+  DeviceBlock<Real> buf;
+  Real *const d = buf.ensure(2 * (size_t)n + 1) == hipSuccess ? buf.ptr : nullptr;
+  if (!d) {
     set_error("dlevmar_R2(): hipMalloc failed");
     return kLmError;
   }
@@ -560,7 +552,6 @@ int r2_run_t(const Real *x, const Real *hx, int n, Real *r2) {
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(r2, d + 2 * (size_t)n, sizeof(Real), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
   if (e != hipSuccess) {
     set_error("dlevmar_R2(): %s", hipGetErrorString(e));
     return kLmError;

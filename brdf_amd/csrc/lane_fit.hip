@@ -295,11 +295,6 @@ LaneFn lane_kernel_w(int model, bool fast) {
   };
   return table[fast ? 1 : 0][model];
 }
-int lane_waves_per_simd() {
-  const char *e = getenv("BRDF_HIP_LANE_WAVES");
-  const int w = e ? atoi(e) : 1;  // measured (2^20 Blinn-Phong fits): 1.43e7 / 1.12e7 / 5.5e6 fits/s at 1 / 2 / 4 (spills beat occupancy)
-  return (w == 2 || w == 4) ? w : 1;
-}
 LaneFn lane_kernel(int model, bool fast, int w) {
   return w == 1 ? lane_kernel_w<1>(model, fast) : (w == 4 ? lane_kernel_w<4>(model, fast) : lane_kernel_w<2>(model, fast));
 }
@@ -318,26 +313,15 @@ int lane_fit_enqueue(int model, bool fast, const BatchCtx &c, int *queue, hipStr
   if (per_cu > 4 * w) per_cu = 4 * w;
   if (per_cu < 1) per_cu = 1;
   BatchCtx cc = c;
-  cc.lane_quorum = 24;  // measured (2^20 fits, one wave per SIMD): quorum 1 (no gating) 1.18e7, 8 1.38e7, 16 1.44e7, 24 1.47e7, 32 1.45e7, 40 1.37e7 fits/s
-  cc.lane_maxwait = 6;
-  if (const char *e = getenv("BRDF_HIP_LANE_QUORUM")) cc.lane_quorum = std::max(1, atoi(e));
-  if (const char *e = getenv("BRDF_HIP_LANE_MAXWAIT")) cc.lane_maxwait = std::max(0, atoi(e));
+  cc.lane_quorum = (int)switch_number(kSwLaneQuorum);
+  cc.lane_maxwait = (int)switch_number(kSwLaneMaxwait);
   long long waves = (long long)cus * per_cu;
   const long long need = ((long long)c.S + kWave - 1) / kWave;
   if (waves > need) waves = need;
-  if (fast) {
-    hipLaunchKernelGGL(lane_kernel(model, true, w), dim3((unsigned)waves), dim3(kWave), lds, stream, cc, queue);
-    HIP_OK(hipGetLastError());
-    if (model != MODEL_WARD) {  // (a launch over an empty set costs one queue sweep: every lane's first fetch finds no marked fit)
-      hipLaunchKernelGGL(lane_kernel(model, false, w), dim3((unsigned)waves), dim3(kWave), lds, stream, cc, queue + 1);
-      HIP_OK(hipGetLastError());
-    }
-  } else {
-    HIP_OK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.flags), kNeedsExact, (size_t)c.S, stream));
-    hipLaunchKernelGGL(lane_kernel(model, false, w), dim3((unsigned)waves), dim3(kWave), lds, stream, cc, queue);
-    HIP_OK(hipGetLastError());
-  }
-  return 0;
+  // (a launch over an empty set costs one queue sweep: every lane's first fetch finds no marked fit)
+  return launch_fast_then_exact(fast, model != MODEL_WARD, c.flags, (size_t)c.S, queue, stream, [&](bool fast_kernel, int *q) {
+    hipLaunchKernelGGL(lane_kernel(model, fast_kernel, w), dim3((unsigned)waves), dim3(kWave), lds, stream, cc, q);
+  });
 }
 
 #ifdef BRDF_LANE_STAMPS

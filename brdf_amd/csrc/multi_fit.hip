@@ -16,7 +16,7 @@
 #include <vector>
 
 #include "../../include/brdf_levmar.h"
-#include "stream_fit.h"
+#include "fit_host.h"
 
 using namespace brdf;
 
@@ -56,15 +56,6 @@ struct Worker {
   std::string err;
 };
 
-template <typename T>
-struct DevArray {
-  T *ptr = nullptr;
-  ~DevArray() {
-    if (ptr) (void)hipFree(ptr);
-  }
-  hipError_t alloc(size_t count) { return hipMalloc(&ptr, count * sizeof(T)); }
-};
-
 struct Events {
   hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
   ~Events() {
@@ -89,15 +80,15 @@ void run_worker(const Call &c, Worker &w, std::vector<ShardStats> &stats) {
     long long most = 0;
     for (int k : w.shards) most = std::max(most, stats[k].count);
     const size_t sn = (size_t)most * c.n;
-    DevArray<double> d_angles, d_x, d_p, d_info;
-    DevArray<int> d_ret;
+    DeviceBlock<double> d_angles, d_x, d_p, d_info;  // (on w.device, the worker's current device)
+    DeviceBlock<int> d_ret;
     Events ev;
     std::vector<int> tmp_ret(c.ret ? 0 : (size_t)most);
-    e = d_angles.alloc(3 * sn);
-    if (e == hipSuccess) e = d_x.alloc(sn);
-    if (e == hipSuccess) e = d_p.alloc(3 * (size_t)most);
-    if (e == hipSuccess) e = d_info.alloc(10 * (size_t)most);
-    if (e == hipSuccess) e = d_ret.alloc((size_t)most);
+    e = d_angles.ensure(3 * sn);
+    if (e == hipSuccess) e = d_x.ensure(sn);
+    if (e == hipSuccess) e = d_p.ensure(3 * (size_t)most);
+    if (e == hipSuccess) e = d_info.ensure(10 * (size_t)most);
+    if (e == hipSuccess) e = d_ret.ensure((size_t)most);
     for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&ev.e[i]);
     if (e != hipSuccess) fail(first_shard, std::string("allocation failed: ") + hipGetErrorString(e));
     for (size_t i = 0; i < w.shards.size() && w.failed_shard < 0; ++i) {
@@ -159,7 +150,8 @@ int brdf_hip_fit_batch_multi(int method, int model, const double *angles, const 
     set_error("brdf_hip_fit_batch_multi(): bad arguments (need angles, x, p, S > 0, n > 0)");
     return LM_ERROR;
   }
-  if (model < 0 || model >= MODEL_COUNT || method < 0 || method > BRDF_METHOD_DER) {
+  MethodSpec ms;
+  if (model < 0 || model >= MODEL_COUNT || !method_spec(method, &ms)) {
     set_error("brdf_hip_fit_batch_multi(): unknown model %d / method %d", model, method);
     return LM_ERROR;
   }

@@ -5,7 +5,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 
 #include "resident_fit_impl.h"  // (first: the diagnostic builds define LM_STAMP in front of lm_machine.h)
@@ -68,8 +67,8 @@ int resident_attempt(const ResidentKernels &k, bool fast, const StreamFitArgs &a
   c.c1 = a.d_angles + a.n;
   c.c2 = a.d_angles + 2 * (size_t)a.n;
   c.x = a.d_x;
-  c.ctl = reinterpret_cast<ResidentCtl *>(ws.d_block);
-  c.rows = reinterpret_cast<u64 *>(ws.d_block + RWorkspace::off_rows);
+  c.ctl = reinterpret_cast<ResidentCtl *>(ws.block.ptr);
+  c.rows = reinterpret_cast<u64 *>(ws.block.ptr + RWorkspace::off_rows);
   c.groups = c.rows + kRowsGranules;
   c.launch_id = ws.tag_base + 1u;  // (tag_base grows by passes + 2 with every launch)
   for (int i = 0; i < kM; ++i) {
@@ -81,14 +80,14 @@ int resident_attempt(const ResidentKernels &k, bool fast, const StreamFitArgs &a
   for (int i = 0; i < 5; ++i) c.opts[i] = a.opts ? a.opts[i] : 0.0;
   c.itmax = a.itmax;
   c.has_opts = a.opts != nullptr;
-  c.has_lb = a.method == 1 && a.lb != nullptr;
-  c.has_ub = a.method == 1 && a.ub != nullptr;
-  c.has_dscl = a.method == 1 && a.dscl != nullptr;
+  c.has_lb = a.method == kBcMachine && a.lb != nullptr;
+  c.has_ub = a.method == kBcMachine && a.ub != nullptr;
+  c.has_dscl = a.method == kBcMachine && a.dscl != nullptr;
   c.want_covar = a.covar != nullptr;
-  c.multi = pg_candidates();
-  c.chain = dif_chain_candidates();
-  c.spec_jac = bc_spec_jac_enabled() ? 1 : 0;
-  c.dif_fused = dif_fused_enabled() ? 1 : 0;
+  c.multi = (int)switch_number(kSwPgMulti);
+  c.chain = (int)switch_number(kSwDifChain);
+  c.spec_jac = switch_on(kSwSpecJac) ? 1 : 0;
+  c.dif_fused = switch_on(kSwDifFused) ? 1 : 0;
   c.analytic = a.analytic ? 1 : 0;
   c.mbox = ws.d_mbox;
   c.n = a.n;
@@ -100,9 +99,8 @@ int resident_attempt(const ResidentKernels &k, bool fast, const StreamFitArgs &a
   c.trace = nullptr;
   c.trace_epoch = -1;
 #ifdef BRDF_STAMPS
-  c.trace = reinterpret_cast<long long *>(ws.d_block + RWorkspace::off_rows + RWorkspace::rows_bytes);
-  c.trace_epoch = 20;
-  if (const char *e = getenv("BRDF_HIP_RESIDENT_TRACE_EPOCH")) c.trace_epoch = atoi(e);
+  c.trace = reinterpret_cast<long long *>(ws.block.ptr + RWorkspace::off_rows + RWorkspace::rows_bytes);
+  c.trace_epoch = (int)switch_number(kSwResidentTraceEpoch);
 #endif
 
   const ResidentKernelFn kernel = k.single[fast ? kFastPath : kExactPath];
@@ -140,15 +138,8 @@ int resident_attempt(const ResidentKernels &k, bool fast, const StreamFitArgs &a
 
 // the fast model path first; the exact one where that is switched off, or met a cosine <= 0 (Ward has no exact path)
 int resident_run(const ResidentKernels &k, const StreamFitArgs &a, RWorkspace &ws, bool *unavailable) {
-  bool retry = false;
-  double keep[kM];
-  for (int i = 0; i < kM; ++i) keep[i] = a.p[i];
-  if (brdf_fast_path_enabled() || !k.single[kExactPath]) {
-    const int ret = resident_attempt(k, true, a, ws, &retry, unavailable);
-    if (!retry || *unavailable) return ret;
-    for (int i = 0; i < kM; ++i) a.p[i] = keep[i];
-  }
-  return k.single[kExactPath] ? resident_attempt(k, false, a, ws, &retry, unavailable) : kLmError;
+  return with_exact_retry(a.p, kM, brdf_fast_path_enabled(), k.single[kExactPath] != nullptr,
+                          [&](bool fast, bool *retry) { return resident_attempt(k, fast, a, ws, retry, unavailable); });
 }
 
 }  // namespace
@@ -166,26 +157,14 @@ int resident_batch_enqueue(int model, int method, bool fast, const BatchCtx &c, 
     return kLmError;
   }
   const ResidentKernels k = kKernels[model][method]();
-  const dim3 grid(c.S), block(kRThreads);
-  const ResidentCtx none{};
-  if (fast) {
-    hipLaunchKernelGGL(k.batched[kFastPath], grid, block, 0, stream, none, c);
-    HIP_OK(hipGetLastError());
-  }
-  if (k.batched[kExactPath]) {  // fits with a cosine <= 0 marked themselves (or all are marked: exact mode)
-    hipLaunchKernelGGL(k.batched[kExactPath], grid, block, 0, stream, none, c);
-    HIP_OK(hipGetLastError());
-  }
-  return 0;
+  return launch_fast_then_exact(fast, k.batched[kExactPath] != nullptr, c.flags, (size_t)c.S, nullptr, stream, [&](bool fast_kernel, int *) {
+    hipLaunchKernelGGL(k.batched[fast_kernel ? kFastPath : kExactPath], dim3(c.S), dim3(kRThreads), 0, stream, ResidentCtx{}, c);
+  });
 }
 
 // returns true if the resident path handled the fit (*ret is then the solver's return value)
 bool resident_fit_try(const StreamFitArgs &a, int *ret) {
-  // Default for every single fit that fits the chip.  Measured on MI355X, 1M-sample Ward fit: 14.3 us per dlevmar_dif
-  // pass against 19.7 us for the launch chain (the secant Jacobian no longer travels through HBM) and 10.7 us per
-  // dlevmar_bc_dif pass against 11.3 us.  BRDF_HIP_RESIDENT=0: always the launch chain.
-  const char *e = getenv("BRDF_HIP_RESIDENT");
-  if (e && e[0] == '0') return false;
+  if (!switch_on(kSwResident)) return false;  // (the default for every single fit that fits the chip)
   int dev = 0;
   if (!kKernels[a.model][a.method] || hipGetDevice(&dev) != hipSuccess) return false;
   RWorkspace &ws = g_rws;

@@ -61,8 +61,8 @@ struct StreamCtx {
 
 // enqueue-and-wait driver; returns the solver's return value (>=0 iterations, or kLmError)
 struct StreamFitArgs {
-  int method, model;
-  int analytic = 0;  // method 1 only: dlevmar_bc_der with the model's analytic Jacobian instead of finite differences
+  int method, model;  // method: fit_host.h's MethodSpec::machine (0 Dif, 1 Bc, 2 Der), the kernels' template index
+  int analytic = 0;   // MethodSpec::analytic: Jacobian rows from the model's analytic Jacobian instead of finite differences
   const double *d_angles, *d_x;
   int n;
   double *p;
@@ -87,42 +87,6 @@ FitStats stream_fit_last_stats();
 // roofline reads it; off by default: two event records and one event wait per fit)
 bool launch_timing_enabled();
 void set_launch_timing(bool on);
-// an event pair per host thread, created on first use (fit_host.h: ResidentWorkspace)
-struct LaunchTimer {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int device = -1;  // the events belong to the device they were created on
-  bool armed = false;
-  void drop() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    e0 = e1 = nullptr;
-  }
-  ~LaunchTimer() { drop(); }
-  void before(hipStream_t s) {
-    armed = false;
-    if (!launch_timing_enabled()) return;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return;
-    if (dev != device) {
-      drop();
-      device = dev;
-    }
-    if (!e0 && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) {
-      drop();
-      return;
-    }
-    armed = hipEventRecord(e0, s) == hipSuccess;
-  }
-  void after(hipStream_t s) {
-    if (armed) armed = hipEventRecord(e1, s) == hipSuccess;
-  }
-  double elapsed_us() {  // after the launch is known to have finished
-    float ms = 0.0f;
-    if (!armed || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) return -1.0;
-    return 1e3 * (double)ms;
-  }
-};
-
 // resident single-launch regime (resident_fit.hip): true if it handled the fit
 bool resident_fit_try(const StreamFitArgs &a, int *ret);
 FitStats resident_fit_last_stats();
@@ -151,12 +115,8 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
                     const double *opts, double *d_brdf_surfaces, double *avg, long long *n_pixels, hipStream_t stream,
                     double *d_surface_covar = nullptr, double *d_surface_stats = nullptr, int *d_surface_rank = nullptr);  // the optional statistics tail
 
-bool brdf_fast_path_enabled();  // false when BRDF_HIP_EXACT_POW=1
-int pg_candidates();            // BRDF_HIP_PG_MULTI (default kMaxCand)
-int dif_chain_candidates();     // BRDF_HIP_DIF_CHAIN (default kMaxCand): dlevmar_dif trial points per sweep in a chain of rejections
-bool dif_fused_enabled();       // BRDF_HIP_DIF_FUSED (default on): resident dlevmar_dif steps try DifMachine::fused_trial_step first
-bool bc_spec_jac_enabled();     // BRDF_HIP_SPEC_JAC (default on): single fits evaluate dlevmar_bc_dif candidates by Jacobian passes
-void set_error(const char *fmt, ...);
-const char *get_error();
+// one model evaluation / analytic Jacobian over n samples (stream_fit.hip): d_hx [n], d_jac [n][3]
+int model_eval_run(int model, const double *d_angles, int n, const double *p, double *d_hx, hipStream_t stream);
+int model_jac_run(int model, const double *d_angles, int n, const double *p, double *d_jac, hipStream_t stream);
 
 }  // namespace brdf

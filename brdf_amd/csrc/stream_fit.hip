@@ -12,7 +12,6 @@
 // workgroups {b, b+8, ...} that share an XCD own one contiguous eighth of the arrays, i.e. every
 // XCD's private L2 keeps seeing the same 1/8 slice on every pass.
 #include <chrono>
-#include <cstdarg>
 #include <cstdio>
 #include <atomic>
 #include <cstdlib>
@@ -449,75 +448,49 @@ __global__ __launch_bounds__(256) void model_jac_kernel(const double *__restrict
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-void set_error(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  fprintf(stderr, "libbrdf_hip: %s\n", g_err);
-}
-const char *get_error() { return g_err; }
-
 namespace {
 
 struct Workspace {
   int device = -1;
-  StreamCtx *d_ctx = nullptr;
+  DeviceBlock<StreamCtx> d_ctx;
   StreamCtx *h_ctx = nullptr;  // pinned staging
   Mailbox *h_mbox = nullptr;   // pinned + mapped
   Mailbox *d_mbox = nullptr;
-  double *d_partials = nullptr;
-  double *d_dif = nullptr;  // per-sample scratch: 2n prepared planes + (dif) 6n = two SoA secant Jacobians
-  size_t dif_cap = 0;
+  DeviceBlock<double> d_partials;
+  DeviceBlock<double> d_dif;  // per-sample scratch, 8n: 2n prepared planes + (dif) 6n = two SoA secant Jacobians
   hipStream_t last_stream = nullptr;
   bool used = false;
   FitStats stats{};
 
   int ensure(int dev) {
-    if (device == dev && d_ctx) return 0;
+    if (device == dev && d_ctx.ptr) return 0;
     release();
     device = dev;
-    HIP_OK(hipMalloc(&d_ctx, sizeof(StreamCtx)));
+    HIP_OK(d_ctx.ensure(1, dev));
     HIP_OK(hipHostMalloc(&h_ctx, sizeof(StreamCtx), hipHostMallocDefault));
     HIP_OK(hipHostMalloc(&h_mbox, sizeof(Mailbox), hipHostMallocMapped | hipHostMallocCoherent));
     HIP_OK(hipHostGetDevicePointer((void **)&d_mbox, h_mbox, 0));
-    HIP_OK(hipMalloc(&d_partials, sizeof(double) * 2 * kSlots * kStreamMaxBlocks));
-    HIP_OK(hipMemset(d_partials, 0, sizeof(double) * 2 * kSlots * kStreamMaxBlocks));
+    HIP_OK(d_partials.ensure((size_t)2 * kSlots * kStreamMaxBlocks, dev));
+    HIP_OK(hipMemset(d_partials.ptr, 0, sizeof(double) * 2 * kSlots * kStreamMaxBlocks));
     return 0;
   }
   int ensure_dif(size_t n) {
-    if (dif_cap >= n) return 0;
-    if (d_dif) (void)hipFree(d_dif);
-    d_dif = nullptr;
-    dif_cap = 0;
-    HIP_OK(hipMalloc(&d_dif, sizeof(double) * 8 * n));
-    dif_cap = n;
+    HIP_OK(d_dif.ensure(8 * n, device));
     return 0;
   }
+  // the blocks go back on their device; a host thread that ends gives them back too (its fits are synchronous)
   void release() {
-    if (d_ctx) (void)hipFree(d_ctx);
+    d_ctx.release();
+    d_partials.release();
+    d_dif.release();
+    DeviceScope on(device);
     if (h_ctx) (void)hipHostFree(h_ctx);
     if (h_mbox) (void)hipHostFree(h_mbox);
-    if (d_partials) (void)hipFree(d_partials);
-    if (d_dif) (void)hipFree(d_dif);
-    d_ctx = nullptr;
     h_ctx = nullptr;
     h_mbox = nullptr;
     d_mbox = nullptr;
-    d_partials = nullptr;
-    d_dif = nullptr;
-    dif_cap = 0;
   }
-  // a host thread that ends gives its blocks back (its fits are synchronous: nothing of them is in flight), on their device
-  ~Workspace() {
-    if (!d_ctx && !d_dif) return;
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    if (device >= 0 && cur != device) (void)hipSetDevice(device);
-    release();
-    if (cur >= 0 && device >= 0 && cur != device) (void)hipSetDevice(cur);
-  }
+  ~Workspace() { release(); }
 };
 thread_local Workspace g_ws;
 
@@ -562,24 +535,24 @@ static int stream_fit_attempt(const StreamFitArgs &a, bool fast, bool *retry_exa
   h.c1 = a.d_angles + a.n;
   h.c2 = a.d_angles + 2 * (size_t)a.n;
   h.x = a.d_x;
-  h.partials = ws.d_partials;
+  h.partials = ws.d_partials.ptr;
   h.mbox = ws.d_mbox;
   h.n = a.n;
   h.nb = blocks_for(a.n);
   h.method = a.method;
   h.model = a.model;
   if (ws.ensure_dif((size_t)a.n) != 0) return kLmError;
-  h.prep[0] = ws.d_dif;
-  h.prep[1] = ws.d_dif + (size_t)a.n;
-  h.jac[0] = ws.d_dif + 2 * (size_t)a.n;
-  h.jac[1] = ws.d_dif + 5 * (size_t)a.n;
+  h.prep[0] = ws.d_dif.ptr;
+  h.prep[1] = ws.d_dif.ptr + (size_t)a.n;
+  h.jac[0] = ws.d_dif.ptr + 2 * (size_t)a.n;
+  h.jac[1] = ws.d_dif.ptr + 5 * (size_t)a.n;
 
   if (start_fit_machine(h.m[0], a.method, a.p, a.n, a.lb, a.ub, a.dscl, a.itmax, a.opts, a.covar != nullptr, a.analytic != 0, fast) != 0)
     return kLmError;  // (h.m[0]: the machine the launches start from)
 
   Mailbox &mb = *ws.h_mbox;
   memset(&mb, 0, sizeof mb);
-  HIP_OK(hipMemcpyAsync(ws.d_ctx, &h, sizeof h, hipMemcpyHostToDevice, a.stream));
+  HIP_OK(hipMemcpyAsync(ws.d_ctx.ptr, &h, sizeof h, hipMemcpyHostToDevice, a.stream));
 
   const PassFn fn = pass_kernel(a.model, a.method, fast);
   const dim3 grid(h.nb), block(kStreamThreads);
@@ -597,7 +570,7 @@ static int stream_fit_attempt(const StreamFitArgs &a, bool fast, bool *retry_exa
         (void)hipStreamSynchronize(a.stream);
         return kLmError;
       }
-      hipLaunchKernelGGL(fn, grid, block, 0, a.stream, ws.d_ctx, (int)pass);
+      hipLaunchKernelGGL(fn, grid, block, 0, a.stream, ws.d_ctx.ptr, (int)pass);
       ++pass;
       if ((pass & 63) == 0) HIP_OK(hipGetLastError());
     } else if ((++spins & 0xFFFF) == 0) {
@@ -620,10 +593,10 @@ static int stream_fit_attempt(const StreamFitArgs &a, bool fast, bool *retry_exa
   ws.stats.launches = pass;
   ws.stats.kernel_us = -1.0;  // (a chain of launches with host decisions in between: timed by its callers' events)
 #ifdef BRDF_STAMPS
-  if (const char *path = getenv("BRDF_HIP_STEP_DUMP")) {  // diagnostic: per-pass cost of the LM step by transition
+  if (const char *path = switch_text(kSwStepDump)) {  // diagnostic: per-pass cost of the LM step by transition
     static StreamCtx tmp;
     (void)hipStreamSynchronize(a.stream);
-    (void)hipMemcpy(&tmp, ws.d_ctx, sizeof tmp, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(&tmp, ws.d_ctx.ptr, sizeof tmp, hipMemcpyDeviceToHost);
     long long ls[8];
     if (hipMemcpyFromSymbol(ls, HIP_SYMBOL(g_lm_stamps), sizeof ls) == hipSuccess) {
       fprintf(stderr, "lm step sections (cycles, summed over %d passes, cumulative since load): after_trial=%lld top+gradient=%lld lu_solve=%lld rest_of_solve=%lld\n",
@@ -638,51 +611,16 @@ static int stream_fit_attempt(const StreamFitArgs &a, bool fast, bool *retry_exa
   return mb.ret;
 }
 
-// BRDF_HIP_PG_MULTI=k: candidates per sweep in bc_dif's projected-gradient search (default 8, 1 = one at a time)
-int pg_candidates() {
-  const char *e = getenv("BRDF_HIP_PG_MULTI");
-  const int k = e ? atoi(e) : kMaxCand;
-  return k < 1 ? 1 : (k > kMaxCand ? kMaxCand : k);
-}
-
-// BRDF_HIP_DIF_CHAIN=k: dlevmar_dif trial points per sweep in a chain of rejections (lm_machine.h: DifMachine::Cold::multi;
-// default 8, 1 = one at a time)
 static std::atomic<int> g_launch_timing{0};
 bool launch_timing_enabled() { return g_launch_timing.load(std::memory_order_relaxed) != 0; }
 void set_launch_timing(bool on) { g_launch_timing.store(on ? 1 : 0, std::memory_order_relaxed); }
-
-int dif_chain_candidates() {
-  const char *e = getenv("BRDF_HIP_DIF_CHAIN");
-  const int k = e ? atoi(e) : kMaxCand;
-  return k < 1 ? 1 : (k > kMaxCand ? kMaxCand : k);
-}
-
-// BRDF_HIP_DIF_FUSED=0: the resident dlevmar_dif kernels step every pass with the machine's generic run() (default: the step behind
-// a trial pass tries the fused trial -> trial transition first, lm_machine.h: DifMachine::fused_trial_step; same results)
-bool dif_fused_enabled() {
-  const char *e = getenv("BRDF_HIP_DIF_FUSED");
-  return !(e && e[0] == '0');
-}
-
-// BRDF_HIP_SPEC_JAC=0: single dlevmar_bc_dif / bc_der fits evaluate their candidates by plain evaluation passes (default: by
-// Jacobian passes, lm_machine.h: BcMachine::Cold::spec_jac)
-bool bc_spec_jac_enabled() {
-  const char *e = getenv("BRDF_HIP_SPEC_JAC");
-  return !(e && e[0] == '0');
-}
-
-// BRDF_HIP_EXACT_POW=1 forces the exact model path (reference expression, pow per evaluation)
-bool brdf_fast_path_enabled() {
-  const char *e = getenv("BRDF_HIP_EXACT_POW");
-  return !(e && e[0] == '1');
-}
 
 int stream_fit_run(const StreamFitArgs &a) {
   if (a.model < 0 || a.model >= MODEL_COUNT) {
     set_error("unknown BRDF model %d (0 Phong, 1 Blinn-Phong, 2 Ward)", a.model);
     return kLmError;
   }
-  if (a.method != 0 && a.method != 1 && a.method != 2) {
+  if (a.method != kDifMachine && a.method != kBcMachine && a.method != kDerMachine) {
     set_error("unknown method %d (0 dlevmar_dif, 1 dlevmar_bc_dif / bc_der, 2 dlevmar_der)", a.method);
     return kLmError;
   }
@@ -714,13 +652,8 @@ int stream_fit_run(const StreamFitArgs &a) {
     for (int i = 0; i < kM; ++i) a.p[i] = p_keep[i];
     g_last_was_resident = false;
   }
-  bool retry = false;
-  int ret = stream_fit_attempt(a, brdf_fast_path_enabled(), &retry);
-  if (retry) {  // a cosine <= 0 on the cached-log path: redo with the reference's pow expression
-    for (int i = 0; i < kM; ++i) a.p[i] = p_keep[i];
-    ret = stream_fit_attempt(a, false, &retry);
-  }
-  return ret;
+  // a cosine <= 0 on the cached-log path: redone with the reference's pow expression
+  return with_exact_retry(a.p, kM, brdf_fast_path_enabled(), true, [&](bool fast, bool *retry) { return stream_fit_attempt(a, fast, retry); });
 }
 
 int model_jac_run(int model, const double *d_angles, int n, const double *p, double *d_jac, hipStream_t stream) {

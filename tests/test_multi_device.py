@@ -266,6 +266,52 @@ def test_multi_two_gpus(gpu):
 
 
 @pytest.mark.gpu
+def test_one_thread_moves_between_devices(gpu):
+    """One host thread fits on device 0, makes device 1 current (hipSetDevice) and fits there, goes back to device 0 and fits
+    again (and once more on device 1): the drop-in dlevmar_bc_dif and brdf_hip_fit_dev at n = 256, brdf_hip_fit_batch_dev at
+    n = 16, S = 64.  The thread's staging block, workspaces and batch scratch each belong to the device they were allocated on
+    and move when the current device does.  Every later round on a device is bit-identical to the first one there, and the
+    thread's brdf_hip_last_error() stays empty.  (A thread of its own: the error text and the workspaces are per thread, so it
+    starts from none and gives everything back, on the owning devices, when it ends.)"""
+    torch, brdf_amd = gpu
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two GPUs (this box has one)")
+    model = 1
+    a1, x1 = synth.make_single(model, 256)[:2]
+    a16, x16, p16 = _inputs(model, 16, 64)
+    kw = dict(lb=synth.LB, ub=synth.UB, itmax=synth.ITMAX, opts=synth.OPTS)
+    rounds, errors = [], []
+
+    def one_round(d):
+        torch.cuda.set_device(d)
+        dev = torch.device("cuda", d)
+        host = brdf_amd.host_dlevmar(1, model, a1, x1, synth.P0[model], **kw)
+        single = brdf_amd.fit_single(1, model, torch.from_numpy(a1).to(dev), torch.from_numpy(x1).to(dev), synth.P0[model], **kw)
+        batch = brdf_amd.fit_batch(1, model, torch.from_numpy(a16).to(dev), torch.from_numpy(x16).to(dev), torch.from_numpy(p16).to(dev), **kw)
+        torch.cuda.synchronize(dev)
+        return [np.array([host.ret, single.ret]), host.p, host.info, single.p, single.info] + [t.cpu().numpy() for t in batch]
+
+    def run():
+        try:
+            for d in (0, 1, 0, 1):
+                rounds.append((d, one_round(d), brdf_amd.last_error()))
+        except Exception as exc:  # reported below
+            errors.append(exc)
+
+    t = threading.Thread(target=run)
+    t.start()
+    t.join(timeout=120)
+    assert not t.is_alive() and not errors, errors
+    first = {}
+    for d, got, err in rounds:
+        assert err == "", (d, err)
+        assert got[0].min() >= 0 and got[-1].min() >= 0, (d, got[0], got[-1])
+        ref = first.setdefault(d, got)
+        assert all(np.array_equal(g, r) for g, r in zip(got, ref)), d
+    assert len(rounds) == 4
+
+
+@pytest.mark.gpu
 def test_cpp_caller_runs(gpu, tmp_path):
     """a C++ program: brdf_hip_fit_batch_multi on {0,0} against brdf_hip_fit_batch (memcmp), then a clean exit"""
     exe = _compile_caller(tmp_path)
