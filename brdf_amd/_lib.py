@@ -61,6 +61,12 @@ ABI = {
     "brdf_hip_fit_stats_batch_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, D, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "brdf_hip_fit_stats_batch": (C.c_int, [C.c_int, C.c_int, D, D, C.c_int, C.c_int, D, D, D, D, I]),
+    "brdf_hip_fit_batch_ragged_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, D, D,
+                                                C.c_int, D, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "brdf_hip_fit_batch_ragged": (C.c_int, [C.c_int, C.c_int, D, D, I, C.c_int, C.c_int, D, D, D, C.c_int, D, D, I]),
+    "brdf_hip_fit_stats_batch_ragged_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, D,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "brdf_hip_fit_stats_batch_ragged": (C.c_int, [C.c_int, C.c_int, D, D, I, C.c_int, C.c_int, D, D, D, D, I]),
     "brdf_hip_model_eval_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, D, C.c_void_p, C.c_void_p]),
     "brdf_hip_synth_dev": (C.c_int, [C.c_int, C.c_ulonglong, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
@@ -73,6 +79,10 @@ ABI = {
     "brdf_hip_fit_capture_stats_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, C.c_void_p, D,
                                                  C.POINTER(C.c_longlong), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "brdf_hip_fit_capture_masked_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, C.c_void_p, D,
+                                                  C.POINTER(C.c_longlong), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                  C.c_double, C.c_void_p]),
     "brdf_hip_fit_capture_single_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, D, D,
                                                   C.POINTER(C.c_longlong), C.c_void_p]),

@@ -4,6 +4,8 @@
 // dlevmar_bc_dif call (brdfdata.cpp:1119).
 #pragma once
 
+#include <type_traits>
+
 #include "device_common.h"
 
 namespace brdf {
@@ -19,6 +21,8 @@ struct BatchFitArgs {
   double *d_info;
   int *d_ret;
   hipStream_t stream;
+  // ragged batch (device, [S], or null): fit s uses samples [0, d_counts[s]) of its rows; n stays the row stride
+  const int *d_counts = nullptr;
 };
 int batch_fit_enqueue(const BatchFitArgs &a);
 
@@ -42,14 +46,35 @@ struct BatchCtx {
   double opts[5], lb[kM], ub[kM];
 };
 
+// what the RAGGED kernel instances take instead: n is the row stride there, counts[S] the fits' own sample counts.  (A type of its
+// own: the uniform kernels' argument block, and with it their code, stays what it was.)
+struct RaggedBatchCtx : BatchCtx {
+  const int *counts;
+};
+template <bool RAGGED>
+using BatchCtxOf = typename std::conditional<RAGGED, RaggedBatchCtx, BatchCtx>::type;
+inline RaggedBatchCtx ragged_ctx(const BatchCtx &c, const int *counts) {
+  RaggedBatchCtx r;
+  static_cast<BatchCtx &>(r) = c;
+  r.counts = counts;
+  return r;
+}
+
+// a ragged fit's own sample count: the fit's entry of counts[], or 0 -- levmar's n < m refusal -- where the entry is outside [0, stride]
+__device__ __forceinline__ int ragged_count(const int *counts, long long fit, int stride) {
+  const int k = counts[fit];
+  return (k < 0 || k > stride) ? 0 : k;
+}
+
 // 1024 < n <= 4096 samples per fit: one workgroup per fit, control wave + seven sample waves (resident_fit.hip).
 // fast = false: only the fits whose flag is kNeedsExact are fitted (exact model path)
-int resident_batch_enqueue(int model, int method, bool fast, const BatchCtx &c, hipStream_t stream);
+// counts (device, [S], or null): per-fit sample counts -- the RAGGED instances
+int resident_batch_enqueue(int model, int method, bool fast, const BatchCtx &c, const int *counts, hipStream_t stream);
 
 
 // n <= kLaneMaxN, dlevmar_bc_dif: one lane per fit (lane_fit.hip).  queue: two zeroed ints
 constexpr int kLaneMaxN = 16;
-int lane_fit_enqueue(int model, bool fast, const BatchCtx &c, int *queue, hipStream_t stream);
+int lane_fit_enqueue(int model, bool fast, const BatchCtx &c, const int *counts, int *queue, hipStream_t stream);
 
 int synth_enqueue(int model, unsigned long long seed, long long first, int count, int n, const double *d_truth,
                   double *d_angles, double *d_x, hipStream_t stream);

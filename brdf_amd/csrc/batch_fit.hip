@@ -31,8 +31,10 @@ using BatchMachine = typename std::conditional<METHOD == 0, DifMachine<kM>, type
 template <int THREADS, int SPT>
 constexpr int batch_waves_per_simd() { return (THREADS == 64 && SPT == 1) ? 4 : 2; }
 
-template <int MODEL, int METHOD, bool FAST, int THREADS, int SPT>
-__global__ __launch_bounds__(THREADS, (batch_waves_per_simd<THREADS, SPT>())) void batch_fit_kernel(BatchCtx ctx) {
+// RAGGED: a second instantiation in which the fit's own count (RaggedBatchCtx::counts, one scalar load) takes n's place everywhere but
+// in the row base and the plane offsets, which keep the stride ctx.n.  The uniform instances are the code they were.
+template <int MODEL, int METHOD, bool FAST, int THREADS, int SPT, bool RAGGED = false>
+__global__ __launch_bounds__(THREADS, (batch_waves_per_simd<THREADS, SPT>())) void batch_fit_kernel(BatchCtxOf<RAGGED> ctx) {
   using Machine = BatchMachine<METHOD>;
   using Mdl = BrdfModel<MODEL>;
   __shared__ Machine sm;
@@ -45,14 +47,17 @@ __global__ __launch_bounds__(THREADS, (batch_waves_per_simd<THREADS, SPT>())) vo
   const int fit = blockIdx.x;
   const int tid = threadIdx.x;
   const bool first_wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x) < kWave;  // see stream_fit.hip
-  const int n = ctx.n;
+  const int stride = ctx.n;
+  int n_ = stride;
+  if constexpr (RAGGED) n_ = ragged_count(ctx.counts, fit, stride);
+  const int n = n_;
   if (!FAST && ctx.flags[fit] != kNeedsExact) return;  // exact kernel: only the fits the fast kernel declined
 
   // ---- the fit's samples: one HBM read, then registers --------------------------------------------------
-  const double *__restrict__ c0 = ctx.angles + (size_t)fit * 3 * n;
-  const double *__restrict__ c1 = c0 + n;
-  const double *__restrict__ c2 = c0 + 2 * (size_t)n;
-  const double *__restrict__ xs = ctx.x + (size_t)fit * n;
+  const double *__restrict__ c0 = ctx.angles + (size_t)fit * 3 * stride;
+  const double *__restrict__ c1 = c0 + stride;
+  const double *__restrict__ c2 = c0 + 2 * (size_t)stride;
+  const double *__restrict__ xs = ctx.x + (size_t)fit * stride;
   double s0[SPT], sx[SPT];
   Prep pq[SPT];
   bool ok[SPT];
@@ -322,8 +327,8 @@ constexpr int kRowsPerWave = kWave / kRowLanes;
 // Occupancy, measured at n = 16 (2^18 fits): dlevmar_dif fits in 128 VGPRs with 39 spilled and still gains from four
 // waves per SIMD (1.65e7 vs 1.17e7 fits/s at two); dlevmar_bc_dif spills 138 VGPRs at that budget and is 4-8 % faster
 // with two waves per SIMD and none spilled.
-template <int MODEL, int METHOD, bool FAST>
-__global__ __launch_bounds__(kWave, (METHOD == 0 ? 4 : 2)) void batch_fit_rows_kernel(BatchCtx ctx, int *queue) {
+template <int MODEL, int METHOD, bool FAST, bool RAGGED = false>
+__global__ __launch_bounds__(kWave, (METHOD == 0 ? 4 : 2)) void batch_fit_rows_kernel(BatchCtxOf<RAGGED> ctx, int *queue) {
   using Machine = BatchMachine<METHOD>;
   using Mdl = BrdfModel<MODEL>;
   __shared__ Machine sm[kRowsPerWave];
@@ -335,7 +340,7 @@ __global__ __launch_bounds__(kWave, (METHOD == 0 ? 4 : 2)) void batch_fit_rows_k
   const int row = lane / kRowLanes;
   const int j = lane % kRowLanes;
   const bool leader = (j == kRowLanes - 1);
-  const int n = ctx.n;
+  const int n = ctx.n;  // the row stride; RAGGED: the fit's own count is per 16-lane row (nfit below)
   Machine &m = sm[row];
   const PassUniforms<MODEL> &u = su[row];
 
@@ -360,7 +365,9 @@ __global__ __launch_bounds__(kWave, (METHOD == 0 ? 4 : 2)) void batch_fit_rows_k
 
     double s0 = 1.0, sx = 0.0, hx = 0.0, wrk = 0.0, jac[kM] = {0.0, 0.0, 0.0};
     Prep pq{1.0, 1.0};
-    const bool ok = row_live && j < n;
+    int nfit = n;
+    if constexpr (RAGGED) nfit = row_live ? ragged_count(ctx.counts, fit, n) : 0;
+    const bool ok = row_live && j < nfit;
     bool declined = false;
     if (row_live) {
       const double *c0 = ctx.angles + (size_t)fit * 3 * n;
@@ -388,9 +395,9 @@ __global__ __launch_bounds__(kWave, (METHOD == 0 ? 4 : 2)) void batch_fit_rows_k
       const double lbv[kM] = {ctx.lb[0], ctx.lb[1], ctx.lb[2]}, ubv[kM] = {ctx.ub[0], ctx.ub[1], ctx.ub[2]};
       const double *opts = ctx.has_opts ? ov : nullptr;
       if constexpr (METHOD == 0)
-        m.start(p0, n, ctx.itmax, opts, 0, /*speculative=*/1);
+        m.start(p0, nfit, ctx.itmax, opts, 0, /*speculative=*/1);
       else
-        m.start(p0, n, ctx.has_lb ? lbv : nullptr, ctx.has_ub ? ubv : nullptr, nullptr, ctx.itmax, opts, 0);
+        m.start(p0, nfit, ctx.has_lb ? lbv : nullptr, ctx.has_ub ? ubv : nullptr, nullptr, ctx.itmax, opts, 0);
     }
     __syncthreads();
 
@@ -554,17 +561,18 @@ __global__ __launch_bounds__(256) void synth_kernel(unsigned long long seed, lon
 // ---------------------------------------------------------------------------------------------------
 namespace {
 
-using BatchFn = void (*)(BatchCtx);
+template <bool R>
+using BatchFn = void (*)(BatchCtxOf<R>);
 
-template <int THREADS, int SPT>
-BatchFn pick(int model, int method, bool fast) {
-  static const BatchFn table[2][MODEL_COUNT][3] = {
-      {{batch_fit_kernel<0, 0, false, THREADS, SPT>, batch_fit_kernel<0, 1, false, THREADS, SPT>, batch_fit_kernel<0, 2, false, THREADS, SPT>},
-       {batch_fit_kernel<1, 0, false, THREADS, SPT>, batch_fit_kernel<1, 1, false, THREADS, SPT>, batch_fit_kernel<1, 2, false, THREADS, SPT>},
+template <int THREADS, int SPT, bool R>
+BatchFn<R> pick(int model, int method, bool fast) {
+  static const BatchFn<R> table[2][MODEL_COUNT][3] = {
+      {{batch_fit_kernel<0, 0, false, THREADS, SPT, R>, batch_fit_kernel<0, 1, false, THREADS, SPT, R>, batch_fit_kernel<0, 2, false, THREADS, SPT, R>},
+       {batch_fit_kernel<1, 0, false, THREADS, SPT, R>, batch_fit_kernel<1, 1, false, THREADS, SPT, R>, batch_fit_kernel<1, 2, false, THREADS, SPT, R>},
        {nullptr, nullptr, nullptr}},  // Ward's prepared path has no domain restriction: no exact twin needed
-      {{batch_fit_kernel<0, 0, true, THREADS, SPT>, batch_fit_kernel<0, 1, true, THREADS, SPT>, batch_fit_kernel<0, 2, true, THREADS, SPT>},
-       {batch_fit_kernel<1, 0, true, THREADS, SPT>, batch_fit_kernel<1, 1, true, THREADS, SPT>, batch_fit_kernel<1, 2, true, THREADS, SPT>},
-       {batch_fit_kernel<2, 0, true, THREADS, SPT>, batch_fit_kernel<2, 1, true, THREADS, SPT>, batch_fit_kernel<2, 2, true, THREADS, SPT>}},
+      {{batch_fit_kernel<0, 0, true, THREADS, SPT, R>, batch_fit_kernel<0, 1, true, THREADS, SPT, R>, batch_fit_kernel<0, 2, true, THREADS, SPT, R>},
+       {batch_fit_kernel<1, 0, true, THREADS, SPT, R>, batch_fit_kernel<1, 1, true, THREADS, SPT, R>, batch_fit_kernel<1, 2, true, THREADS, SPT, R>},
+       {batch_fit_kernel<2, 0, true, THREADS, SPT, R>, batch_fit_kernel<2, 1, true, THREADS, SPT, R>, batch_fit_kernel<2, 2, true, THREADS, SPT, R>}},
   };
   return table[fast ? 1 : 0][model][method];
 }
@@ -584,11 +592,12 @@ bool geometry_for(int n, Geometry *g) {
   return true;
 }
 
-BatchFn kernel_for(const Geometry &g, int model, int method, bool fast) {
-  if (g.threads == 64 && g.spt == 1) return pick<64, 1>(model, method, fast);
-  if (g.threads == 64 && g.spt == 4) return pick<64, 4>(model, method, fast);
-  if (g.threads == 256) return pick<256, 4>(model, method, fast);
-  return pick<512, 8>(model, method, fast);
+template <bool R>
+BatchFn<R> kernel_for(const Geometry &g, int model, int method, bool fast) {
+  if (g.threads == 64 && g.spt == 1) return pick<64, 1, R>(model, method, fast);
+  if (g.threads == 64 && g.spt == 4) return pick<64, 4, R>(model, method, fast);
+  if (g.threads == 256) return pick<256, 4, R>(model, method, fast);
+  return pick<512, 8, R>(model, method, fast);
 }
 
 // Per-thread scratch of a batch call: flags[S] (kNeedsExact marks, read by the second launch) and two work-queue
@@ -617,15 +626,17 @@ thread_local BatchScratch g_scratch;
 
 namespace {
 
-using RowsFn = void (*)(BatchCtx, int *);
-RowsFn rows_kernel(int model, int method, bool fast) {
-  static const RowsFn table[2][MODEL_COUNT][2] = {
-      {{batch_fit_rows_kernel<0, 0, false>, batch_fit_rows_kernel<0, 1, false>},
-       {batch_fit_rows_kernel<1, 0, false>, batch_fit_rows_kernel<1, 1, false>},
+template <bool R>
+using RowsFn = void (*)(BatchCtxOf<R>, int *);
+template <bool R>
+RowsFn<R> rows_kernel(int model, int method, bool fast) {
+  static const RowsFn<R> table[2][MODEL_COUNT][2] = {
+      {{batch_fit_rows_kernel<0, 0, false, R>, batch_fit_rows_kernel<0, 1, false, R>},
+       {batch_fit_rows_kernel<1, 0, false, R>, batch_fit_rows_kernel<1, 1, false, R>},
        {nullptr, nullptr}},
-      {{batch_fit_rows_kernel<0, 0, true>, batch_fit_rows_kernel<0, 1, true>},
-       {batch_fit_rows_kernel<1, 0, true>, batch_fit_rows_kernel<1, 1, true>},
-       {batch_fit_rows_kernel<2, 0, true>, batch_fit_rows_kernel<2, 1, true>}},
+      {{batch_fit_rows_kernel<0, 0, true, R>, batch_fit_rows_kernel<0, 1, true, R>},
+       {batch_fit_rows_kernel<1, 0, true, R>, batch_fit_rows_kernel<1, 1, true, R>},
+       {batch_fit_rows_kernel<2, 0, true, R>, batch_fit_rows_kernel<2, 1, true, R>}},
   };
   return table[fast ? 1 : 0][model][method];
 }
@@ -638,7 +649,7 @@ RowsFn rows_kernel(int model, int method, bool fast) {
 // (fit_switches.h: rows_path_enabled, BRDF_HIP_ROWS)
 
 // four fits per wavefront, rows pull work from a queue: a few waves per SIMD on every CU are enough
-int rows_enqueue(int model, int machine, const BatchCtx &c, bool fast, int *queue, hipStream_t stream) {
+int rows_enqueue(int model, int machine, const BatchCtx &c, const int *counts, bool fast, int *queue, hipStream_t stream) {
   int dev = 0, cus = 0;
   HIP_OK(hipGetDevice(&dev));
   HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
@@ -646,7 +657,10 @@ int rows_enqueue(int model, int machine, const BatchCtx &c, bool fast, int *queu
   const long long need = ((long long)c.S + kRowsPerWave - 1) / kRowsPerWave;
   if (waves > need) waves = need;
   return launch_fast_then_exact(fast, model != MODEL_WARD, c.flags, (size_t)c.S, queue, stream, [&](bool fast_kernel, int *q) {
-    hipLaunchKernelGGL(rows_kernel(model, machine, fast_kernel), dim3((unsigned)waves), dim3(kWave), 0, stream, c, q);
+    if (counts)
+      hipLaunchKernelGGL(rows_kernel<true>(model, machine, fast_kernel), dim3((unsigned)waves), dim3(kWave), 0, stream, ragged_ctx(c, counts), q);
+    else
+      hipLaunchKernelGGL(rows_kernel<false>(model, machine, fast_kernel), dim3((unsigned)waves), dim3(kWave), 0, stream, c, q);
   });
 }
 
@@ -685,17 +699,20 @@ int batch_fit_launches(const BatchFitArgs &a, MethodSpec ms, const Geometry &g, 
   }
   HIP_OK(hipMemsetAsync(queue, 0, 2 * sizeof(int), a.stream));
   const bool fast = brdf_fast_path_enabled() || a.model == MODEL_WARD;
-  if (a.n <= kLaneMaxN && method == kBcMachine && switch_on(kSwLane)) return lane_fit_enqueue(a.model, fast, c, queue, a.stream);
+  if (a.n <= kLaneMaxN && method == kBcMachine && switch_on(kSwLane)) return lane_fit_enqueue(a.model, fast, c, a.d_counts, queue, a.stream);
   if (a.n <= kRowLanes && method != kDerMachine && !c.analytic && rows_path_enabled(method == kDifMachine))
-    return rows_enqueue(a.model, method, c, fast, queue, a.stream);
+    return rows_enqueue(a.model, method, c, a.d_counts, fast, queue, a.stream);
   if (g.threads == 512 && (switch_on(kSwBatchBig) || method == kDerMachine || c.analytic)) {  // 1024 < n <= 4096: eight waves per fit (resident_fit.hip)
     c.multi = (int)switch_number(kSwPgMulti);
     c.chain = batch_dif_chain();
-    return resident_batch_enqueue(a.model, method, fast, c, a.stream);
+    return resident_batch_enqueue(a.model, method, fast, c, a.d_counts, a.stream);
   }
   // fits with a cosine <= 0 mark themselves: second launch on the exact path (Ward's prepared path has no domain restriction)
   return launch_fast_then_exact(fast, a.model != MODEL_WARD, flags, (size_t)a.S, nullptr, a.stream, [&](bool fast_kernel, int *) {
-    hipLaunchKernelGGL(kernel_for(g, a.model, method, fast_kernel), dim3(a.S), dim3(g.threads), 0, a.stream, c);
+    if (a.d_counts)
+      hipLaunchKernelGGL(kernel_for<true>(g, a.model, method, fast_kernel), dim3(a.S), dim3(g.threads), 0, a.stream, ragged_ctx(c, a.d_counts));
+    else
+      hipLaunchKernelGGL(kernel_for<false>(g, a.model, method, fast_kernel), dim3(a.S), dim3(g.threads), 0, a.stream, c);
   });
 }
 }  // namespace
@@ -707,10 +724,31 @@ namespace {
 int batch_of_large_fits(const BatchFitArgs &a, MethodSpec ms) {
   std::vector<double> p((size_t)a.S * kM), info((size_t)a.S * kInfoSz);
   std::vector<int> ret(a.S);
+  std::vector<int> counts;  // ragged: the counts travel to the host next to p
   HIP_OK(hipMemcpyAsync(p.data(), a.d_p, sizeof(double) * p.size(), hipMemcpyDeviceToHost, a.stream));
+  if (a.d_counts) {
+    counts.resize(a.S);
+    HIP_OK(hipMemcpyAsync(counts.data(), a.d_counts, sizeof(int) * counts.size(), hipMemcpyDeviceToHost, a.stream));
+  }
   HIP_OK(hipStreamSynchronize(a.stream));
+  DeviceBlock<double> pack;  // a ragged fit's three plane prefixes, next to each other as a single fit reads them
   for (int s = 0; s < a.S; ++s) {
-    const StreamFitArgs f = stream_fit_args(ms, a.model, a.d_angles + (size_t)s * 3 * a.n, a.d_x + (size_t)s * a.n, a.n, p.data() + (size_t)s * kM,
+    const double *angles = a.d_angles + (size_t)s * 3 * a.n;
+    int k = a.n;
+    if (a.d_counts) {
+      k = counts[s];
+      if (k < kM || k > a.n) {  // levmar's n < m refusal (lm_core.c:502, lmbc_core.c:440), without a launch: info stays zero, p as it came
+        ret[s] = kLmError;
+        continue;
+      }
+      if (k != a.n) {
+        HIP_OK(pack.ensure(3 * (size_t)a.n));
+        for (int pl = 0; pl < 3; ++pl)
+          HIP_OK(hipMemcpyAsync(pack.ptr + (size_t)pl * k, angles + (size_t)pl * a.n, sizeof(double) * k, hipMemcpyDeviceToDevice, a.stream));
+        angles = pack.ptr;
+      }
+    }
+    const StreamFitArgs f = stream_fit_args(ms, a.model, angles, a.d_x + (size_t)s * a.n, k, p.data() + (size_t)s * kM,
                                             a.lb, a.ub, nullptr, a.itmax, a.opts, info.data() + (size_t)s * kInfoSz, nullptr, a.stream);
     ret[s] = stream_fit_run(f);
   }

@@ -490,27 +490,56 @@ int brdf_hip_fit_batch_dev(int method, int model, const double *d_angles, const 
   return batch_fit_enqueue(a);
 }
 
-int brdf_hip_fit_batch(int method, int model, const double *angles, const double *x, int S, int n, double *p,
-                       const double *lb, const double *ub, int itmax, const double *opts, double *info, int *ret) {
+int brdf_hip_fit_batch_ragged_dev(int method, int model, const double *d_angles, const double *d_x, const int *d_counts, int S, int n,
+                                  double *d_p, const double *lb, const double *ub, int itmax, const double *opts, double *d_info,
+                                  int *d_ret, void *stream) {
+  BatchFitArgs a;
+  a.method = method;
+  a.model = model;
+  a.d_angles = d_angles;
+  a.d_x = d_x;
+  a.d_counts = d_counts;  // (null: the uniform call)
+  a.S = S;
+  a.n = n;
+  a.d_p = d_p;
+  a.lb = lb;
+  a.ub = ub;
+  a.itmax = itmax;
+  a.opts = opts;
+  a.d_info = d_info;
+  a.d_ret = d_ret;
+  a.stream = static_cast<hipStream_t>(stream);
+  return batch_fit_enqueue(a);
+}
+
+namespace {
+// brdf_hip_fit_batch and its ragged twin (counts: host, or null)
+int fit_batch_host(const char *who, int method, int model, const double *angles, const double *x, const int *counts, int S, int n, double *p,
+                   const double *lb, const double *ub, int itmax, const double *opts, double *info, int *ret) {
   if (!angles || !x || !p || S <= 0 || n <= 0) {
-    set_error("brdf_hip_fit_batch(): bad arguments");
+    set_error("%s(): bad arguments", who);
+    return LM_ERROR;
+  }
+  if (counts && (model < 0 || model >= brdf::MODEL_COUNT || method < BRDF_METHOD_DIF || method > BRDF_METHOD_DER)) {  // before any HIP call
+    set_error("%s(): unknown model %d / method %d", who, model, method);
     return LM_ERROR;
   }
   const size_t sn = (size_t)S * n;
-  DevBuf d_angles, d_x, d_p, d_info, d_ret;
+  DevBuf d_angles, d_x, d_p, d_info, d_ret, d_counts;
   if (alloc_doubles(d_angles, 3 * sn) || alloc_doubles(d_x, sn) || alloc_doubles(d_p, 3 * (size_t)S) || alloc_doubles(d_info, 10 * (size_t)S) ||
-      alloc_doubles(d_ret, ((size_t)S + 1) / 2 + 1))
+      alloc_doubles(d_ret, ((size_t)S + 1) / 2 + 1) || (counts && alloc_doubles(d_counts, ((size_t)S + 1) / 2 + 1)))
     return LM_ERROR;
   hipError_t e = hipMemcpy(d_angles.ptr, angles, sizeof(double) * 3 * sn, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_x.ptr, x, sizeof(double) * sn, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_p.ptr, p, sizeof(double) * 3 * S, hipMemcpyHostToDevice);
+  if (e == hipSuccess && counts) e = hipMemcpy(d_counts.ptr, counts, sizeof(int) * S, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    set_error("brdf_hip_fit_batch(): host->device copy failed: %s", hipGetErrorString(e));
+    set_error("%s(): host->device copy failed: %s", who, hipGetErrorString(e));
     return LM_ERROR;
   }
   int *d_ret_i = reinterpret_cast<int *>(d_ret.ptr);
-  if (brdf_hip_fit_batch_dev(method, model, d_angles.ptr, d_x.ptr, S, n, d_p.ptr, lb, ub, itmax, opts, d_info.ptr,
-                             d_ret_i, nullptr) != 0)
+  if (brdf_hip_fit_batch_ragged_dev(method, model, d_angles.ptr, d_x.ptr, counts ? reinterpret_cast<const int *>(d_counts.ptr) : nullptr, S, n,
+                                    d_p.ptr, lb, ub, itmax, opts, d_info.ptr, d_ret_i, nullptr) != 0)
     return LM_ERROR;
   e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy(p, d_p.ptr, sizeof(double) * 3 * S, hipMemcpyDeviceToHost);
@@ -524,10 +553,21 @@ int brdf_hip_fit_batch(int method, int model, const double *angles, const double
     for (int s = 0; s < S; ++s) bad += host_ret[s] < 0;
   delete[] tmp;
   if (e != hipSuccess) {
-    set_error("brdf_hip_fit_batch(): %s", hipGetErrorString(e));
+    set_error("%s(): %s", who, hipGetErrorString(e));
     return LM_ERROR;
   }
   return bad;
+}
+}  // namespace
+
+int brdf_hip_fit_batch(int method, int model, const double *angles, const double *x, int S, int n, double *p,
+                       const double *lb, const double *ub, int itmax, const double *opts, double *info, int *ret) {
+  return fit_batch_host("brdf_hip_fit_batch", method, model, angles, x, nullptr, S, n, p, lb, ub, itmax, opts, info, ret);
+}
+
+int brdf_hip_fit_batch_ragged(int method, int model, const double *angles, const double *x, const int *counts, int S, int n, double *p,
+                              const double *lb, const double *ub, int itmax, const double *opts, double *info, int *ret) {
+  return fit_batch_host("brdf_hip_fit_batch_ragged", method, model, angles, x, counts, S, n, p, lb, ub, itmax, opts, info, ret);
 }
 
 int brdf_hip_fit_stats_batch_dev(int method, int model, const double *d_angles, const double *d_x, int S, int n,
@@ -549,9 +589,29 @@ int brdf_hip_fit_stats_batch_dev(int method, int model, const double *d_angles, 
   return fit_stats_enqueue(a, "brdf_hip_fit_stats_batch_dev");
 }
 
-int brdf_hip_fit_stats_batch(int method, int model, const double *angles, const double *x, int S, int n, const double *p,
-                             const double *opts, double *covar, double *stats, int *rank) {
-  static const char *who = "brdf_hip_fit_stats_batch";
+int brdf_hip_fit_stats_batch_ragged_dev(int method, int model, const double *d_angles, const double *d_x, const int *d_counts, int S,
+                                        int n, const double *d_p, const double *opts, double *d_covar, double *d_stats, int *d_rank,
+                                        void *stream) {
+  FitStatsArgs a;
+  a.method = method;
+  a.model = model;
+  a.d_angles = d_angles;
+  a.d_x = d_x;
+  a.d_counts = d_counts;  // (null: the uniform call)
+  a.S = S;
+  a.n = n;
+  a.d_p = d_p;
+  a.opts = opts;
+  a.d_covar = d_covar;
+  a.d_stats = d_stats;
+  a.d_rank = d_rank;
+  a.stream = static_cast<hipStream_t>(stream);
+  return fit_stats_enqueue(a, "brdf_hip_fit_stats_batch_ragged_dev");
+}
+
+namespace {
+int fit_stats_host(const char *who, int method, int model, const double *angles, const double *x, const int *counts, int S, int n,
+                   const double *p, const double *opts, double *covar, double *stats, int *rank) {
   FitStatsArgs a;
   a.method = method;
   a.model = model;
@@ -566,17 +626,20 @@ int brdf_hip_fit_stats_batch(int method, int model, const double *angles, const 
   a.d_rank = rank;
   if (fit_stats_check(a, who) != 0) return LM_ERROR;
   const size_t sn = (size_t)S * n;
-  DevBuf d_angles, d_x, d_p, d_covar, d_stats, d_rank;
+  DevBuf d_angles, d_x, d_p, d_covar, d_stats, d_rank, d_counts;
   if (alloc_doubles(d_angles, 3 * sn) || alloc_doubles(d_x, sn) || alloc_doubles(d_p, 3 * (size_t)S) || (covar && alloc_doubles(d_covar, 9 * (size_t)S)) ||
-      (stats && alloc_doubles(d_stats, BRDF_STATS_SZ * (size_t)S)) || (rank && alloc_doubles(d_rank, ((size_t)S + 1) / 2 + 1)))
+      (stats && alloc_doubles(d_stats, BRDF_STATS_SZ * (size_t)S)) || (rank && alloc_doubles(d_rank, ((size_t)S + 1) / 2 + 1)) ||
+      (counts && alloc_doubles(d_counts, ((size_t)S + 1) / 2 + 1)))
     return LM_ERROR;
   hipError_t e = hipMemcpy(d_angles.ptr, angles, sizeof(double) * 3 * sn, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_x.ptr, x, sizeof(double) * sn, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_p.ptr, p, sizeof(double) * 3 * S, hipMemcpyHostToDevice);
+  if (e == hipSuccess && counts) e = hipMemcpy(d_counts.ptr, counts, sizeof(int) * S, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     set_error("%s(): host->device copy failed: %s", who, hipGetErrorString(e));
     return LM_ERROR;
   }
+  a.d_counts = counts ? reinterpret_cast<const int *>(d_counts.ptr) : nullptr;
   a.d_angles = d_angles.ptr;
   a.d_x = d_x.ptr;
   a.d_p = d_p.ptr;
@@ -593,6 +656,17 @@ int brdf_hip_fit_stats_batch(int method, int model, const double *angles, const 
     return LM_ERROR;
   }
   return 0;
+}
+}  // namespace
+
+int brdf_hip_fit_stats_batch(int method, int model, const double *angles, const double *x, int S, int n, const double *p,
+                             const double *opts, double *covar, double *stats, int *rank) {
+  return fit_stats_host("brdf_hip_fit_stats_batch", method, model, angles, x, nullptr, S, n, p, opts, covar, stats, rank);
+}
+
+int brdf_hip_fit_stats_batch_ragged(int method, int model, const double *angles, const double *x, const int *counts, int S, int n,
+                                    const double *p, const double *opts, double *covar, double *stats, int *rank) {
+  return fit_stats_host("brdf_hip_fit_stats_batch_ragged", method, model, angles, x, counts, S, n, p, opts, covar, stats, rank);
 }
 
 int brdf_hip_model_eval_dev(int model, const double *d_angles, int n, const double *p, double *d_hx, void *stream) {
@@ -631,6 +705,19 @@ int brdf_hip_fit_capture_stats_dev(int model, const unsigned char *d_images, int
   return capture_fit_run(model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin,
                          rv_mode, p0, lb, ub, itmax, opts, d_brdf_surfaces, avg, n_pixels, static_cast<hipStream_t>(stream),
                          d_surface_covar, d_surface_stats, d_surface_rank);
+}
+
+int brdf_hip_fit_capture_masked_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                    const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf,
+                                    const double *leds, const double *view_origin, int rv_mode, const double *p0,
+                                    const double *lb, const double *ub, int itmax, const double *opts, double *d_brdf_surfaces,
+                                    double *avg, long long *n_pixels, void *stream, double *d_surface_covar,
+                                    double *d_surface_stats, int *d_surface_rank, int v_min, int v_max, double cos_min,
+                                    int *d_surface_count) {
+  const CaptureMask mask = {v_min, v_max, cos_min, d_surface_count};
+  return capture_fit_run(model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin,
+                         rv_mode, p0, lb, ub, itmax, opts, d_brdf_surfaces, avg, n_pixels, static_cast<hipStream_t>(stream),
+                         d_surface_covar, d_surface_stats, d_surface_rank, &mask);
 }
 
 int brdf_hip_fit_capture_single_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,

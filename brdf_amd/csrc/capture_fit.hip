@@ -126,6 +126,73 @@ __global__ __launch_bounds__(kCT) void stats_rows_kernel(const long long *last_o
   src_of_row[r] = last ? (int)(3 * (last - 1) + (r - 3 * f)) : -1;
 }
 
+// ---- the validity rule of brdf_hip_fit_capture_masked_dev --------------------------------------------------------------------
+// sample i of a fit is valid iff v_min <= its 8-bit intensity <= v_max and every cosine plane the model reads is > cos_min (a NaN
+// cosine is not).  x holds intensity / 255.0 (gather_kernel): rint(x * 255) is the intensity again, the product being within an ulp
+// of 255 of it.
+__device__ __forceinline__ bool sample_valid(double c0, double c1, double c2, double xv, int v_min, int v_max, double cos_min, int use1,
+                                             int use2) {
+  const int v = __double2int_rn(xv * 255.0);
+  return v >= v_min && v <= v_max && c0 > cos_min && (!use1 || c1 > cos_min) && (!use2 || c2 > cos_min);
+}
+
+// L = 16: a fit is one 16-lane row of a wave.  Every lane reads its four values; a ballot and the popcount of the row's lower lanes
+// give a valid sample its place at the front of the row (stable in light order); then the lanes write.  A row is read and written by
+// its own sixteen lanes only, and a wave's loads of a plane have all returned before its stores to that plane issue: in place is safe.
+__global__ __launch_bounds__(kCT) void mask_rows16_kernel(double *angles, double *x, long long Q, int v_min, int v_max, double cos_min,
+                                                          int use1, int use2, int *counts) {
+  const long long q = ((long long)blockIdx.x * kCT + threadIdx.x) >> 4;
+  const int i = threadIdx.x & 15, lane = threadIdx.x & 63;
+  double v0 = 0.0, v1 = 0.0, v2 = 0.0, vx = 0.0;
+  bool valid = false;
+  double *a = angles + (size_t)(q < Q ? q : 0) * 48, *xr = x + (size_t)(q < Q ? q : 0) * 16;
+  if (q < Q) {
+    v0 = a[i];
+    v1 = a[16 + i];
+    v2 = a[32 + i];
+    vx = xr[i];
+    valid = sample_valid(v0, v1, v2, vx, v_min, v_max, cos_min, use1, use2);
+  }
+  const unsigned long long m = __ballot(valid);
+  const unsigned row = (unsigned)(m >> (lane & 48)) & 0xffffu;
+  if (valid) {
+    const int d = __popc(row & ((1u << i) - 1u));
+    a[d] = v0;
+    a[16 + d] = v1;
+    a[32 + d] = v2;
+    xr[d] = vx;
+  }
+  if (q < Q && i == 0) counts[q] = __popc(row);
+}
+
+// any other L <= 64: one thread per fit, a serial walk (the write index never passes the read index)
+__global__ __launch_bounds__(kCT) void mask_serial_kernel(double *angles, double *x, long long Q, int L, int v_min, int v_max,
+                                                          double cos_min, int use1, int use2, int *counts) {
+  const long long q = (long long)blockIdx.x * kCT + threadIdx.x;
+  if (q >= Q) return;
+  double *a = angles + (size_t)q * 3 * L, *xr = x + (size_t)q * L;
+  int w = 0;
+  for (int i = 0; i < L; ++i) {
+    const double v0 = a[i], v1 = a[L + i], v2 = a[2 * L + i], vx = xr[i];
+    if (!sample_valid(v0, v1, v2, vx, v_min, v_max, cos_min, use1, use2)) continue;
+    a[w] = v0;
+    a[L + w] = v1;
+    a[2 * L + w] = v2;
+    xr[w] = vx;
+    ++w;
+  }
+  counts[q] = w;
+}
+
+// surface_count(face, channel) <- the sample count of the fit store_kernel's rule stores for it
+__global__ __launch_bounds__(kCT) void count_map_kernel(const long long *last_of_face, int nf, const int *counts, int *surface_count) {
+  const int r = blockIdx.x * kCT + threadIdx.x;
+  if (r >= 3 * nf) return;
+  const int f = r / 3;
+  const long long last = last_of_face[f];
+  if (last) surface_count[r] = counts[3 * (last - 1) + (r - 3 * f)];
+}
+
 // ---- single-BRDF variant (CalcBRDFEquation_SingleBRDF, brdfdata.cpp:1138-1186) --------------------------------
 __global__ __launch_bounds__(kCT) void face_count_kernel(const long long *last_of_face, int nf, int *block_count) {
   __shared__ int wave_cnt[kCT / 64];
@@ -189,9 +256,13 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
                     const double *d_vertices, const int *d_faces, const double *d_normals, int nf, const double *leds,
                     const double *view, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
                     const double *opts, double *d_brdf_surfaces, double *avg, long long *n_pixels, hipStream_t stream,
-                    double *d_surface_covar, double *d_surface_stats, int *d_surface_rank) {
+                    double *d_surface_covar, double *d_surface_stats, int *d_surface_rank, const CaptureMask *mask) {
   const bool want_stats = d_surface_covar || d_surface_stats || d_surface_rank;
-  const char *who = want_stats ? "brdf_hip_fit_capture_stats_dev" : "brdf_hip_fit_capture_dev";
+  const char *who = mask ? "brdf_hip_fit_capture_masked_dev" : (want_stats ? "brdf_hip_fit_capture_stats_dev" : "brdf_hip_fit_capture_dev");
+  if (mask && (mask->v_min > mask->v_max || mask->cos_min != mask->cos_min || model < 0 || model >= MODEL_COUNT)) {
+    set_error("%s(): bad validity rule (v_min %d > v_max %d, or cos_min not a number) or unknown model %d", who, mask->v_min, mask->v_max, model);
+    return kLmError;
+  }
   if (!d_images || !d_pixel_map || !d_vertices || !d_faces || !d_normals || !leds || !view || !p0 || !d_brdf_surfaces ||
       L <= 0 || L > 64 || H <= 0 || W <= 0 || nf <= 0) {
     set_error("%s(): bad arguments", who);
@@ -246,7 +317,21 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
   CAP_OK(hipGetLastError());
   if (cosines_run(d_vertices, d_faces, d_normals, faces3.as<int>(), 3 * S, leds, L, view, rv_mode, angles.as<double>(), stream) != 0)
     return kLmError;
+  DevBuf fit_counts;
+  if (mask) {  // valid samples to the front of every fit's rows, in place; the fits below are ragged
+    const long long Q = 3 * S;
+    const int use1 = model != MODEL_PHONG, use2 = model != MODEL_BLINN_PHONG;  // the planes the model reads (brdf_models.h: uses_c1, uses_c2)
+    CAP_OK(fit_counts.ensure(sizeof(int) * Q));
+    if (L == 16)
+      hipLaunchKernelGGL(mask_rows16_kernel, dim3((unsigned)((Q * 16 + kCT - 1) / kCT)), dim3(kCT), 0, stream, angles.as<double>(), x.as<double>(), Q,
+                         mask->v_min, mask->v_max, mask->cos_min, use1, use2, fit_counts.as<int>());
+    else
+      hipLaunchKernelGGL(mask_serial_kernel, dim3((unsigned)((Q + kCT - 1) / kCT)), dim3(kCT), 0, stream, angles.as<double>(), x.as<double>(), Q, L,
+                         mask->v_min, mask->v_max, mask->cos_min, use1, use2, fit_counts.as<int>());
+    CAP_OK(hipGetLastError());
+  }
   BatchFitArgs a;
+  a.d_counts = mask ? fit_counts.as<int>() : nullptr;
   a.method = BRDF_METHOD_BC_DIF;  // brdfdata.cpp:1119
   a.model = model;
   a.d_angles = angles.as<double>();
@@ -267,6 +352,11 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
   hipLaunchKernelGGL(store_kernel, dim3(sb), dim3(kCT), 0, stream, p.as<double>(), face_s.as<int>(), last.as<long long>(), S,
                      d_brdf_surfaces, sums.as<double>());
   CAP_OK(hipGetLastError());
+  if (mask && mask->d_surface_count) {
+    hipLaunchKernelGGL(count_map_kernel, dim3((3 * nf + kCT - 1) / kCT), dim3(kCT), 0, stream, last.as<long long>(), nf, fit_counts.as<int>(),
+                       mask->d_surface_count);
+    CAP_OK(hipGetLastError());
+  }
   DevBuf src_of_row;
   if (want_stats) {  // the staged angles / x / p are still in HBM: one pass over the stored fits
     CAP_OK(src_of_row.ensure(sizeof(int) * 3 * (size_t)nf));
@@ -285,6 +375,7 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
     fs.d_stats = d_surface_stats;
     fs.d_rank = d_surface_rank;
     fs.d_src = src_of_row.as<int>();
+    fs.d_counts = a.d_counts;
     fs.rows = 3 * nf;
     fs.stream = stream;
     if (fit_stats_enqueue(fs, who) != 0) return kLmError;

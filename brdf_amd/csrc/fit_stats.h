@@ -22,6 +22,10 @@ struct FitStatsArgs {
   const int *d_src = nullptr;
   int rows = 0;
   hipStream_t stream = nullptr;
+  // ragged batch (device, [S], or null): fit s has samples [0, d_counts[s]) of its rows, n is the row stride and the largest count.
+  // Degrees of freedom d_counts[s] - 3; a count below 3 or outside [0, n]: rank 0, zero covar / sd / rho, sumsq and R2 over the samples
+  // there are (both 0 for none).  n > 4096: synchronises the stream (the counts travel to the host; one uniform pass per fit).
+  const int *d_counts = nullptr;
 };
 
 // argument check (no HIP call) and enqueue; `who` names the entry point in error texts.  Asynchronous on a.stream.

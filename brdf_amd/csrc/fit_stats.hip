@@ -27,6 +27,7 @@
 // In the first three the per-fit sums are parked in LDS and the first lanes of the workgroup finish one fit each, so the
 // serial 3 x 3 LU runs in a few dense wavefronts instead of one lane of every wavefront.
 #include <cstdio>
+#include <vector>
 
 #include "../../include/brdf_levmar.h"
 #include "fit_stats.h"
@@ -56,7 +57,14 @@ struct StatsCtx {
   long long rows;
   int n, chunk, nb;
   double delta;  // |opts[4]|, or LM_DIFF_DELTA
+  const int *counts;  // [S] or null: per-fit sample counts (RAGGED kernel instances; n is the row stride there)
 };
+
+// a ragged fit's own sample count: 0 where the entry is outside [0, stride] (nothing of the row is read then)
+__device__ __forceinline__ int stats_count(const StatsCtx &c, long long q) {
+  const int k = c.counts[q];
+  return (k < 0 || k > c.n) ? 0 : k;
+}
 
 __device__ __forceinline__ long long fit_of_row(const StatsCtx &c, long long r) {
   if (r >= c.rows) return -1;
@@ -121,13 +129,15 @@ __device__ __forceinline__ double sample_acc(const JacUniforms &u, const double 
 }
 
 // one lane per fit: row = [sum e^2, J^T J lower (6), sum x, sum (x - mean)^2] -> the fit's outputs
-__device__ __forceinline__ void finish_fit(const StatsCtx &c, long long r, long long q, const double *row) {
+// RAGGED: n is the fit's own count -- below kM there are no degrees of freedom (rank 0), and of no samples both sumsq and R2 are 0
+template <bool RAGGED = false>
+__device__ __forceinline__ void finish_fit(const StatsCtx &c, long long r, long long q, const double *row, int n) {
   double jtj[kM * kM], cv[kM * kM], sd[kM], rho[kM];
   const double sumsq = row[0], sstot = row[kNS];
   unpack_lower<kM>(row + 1, jtj);
 #pragma unroll
   for (int k = 0; k < kM * kM; ++k) cv[k] = 0.0;
-  int rank = lu_covar<kM>(jtj, cv, sumsq, c.n);
+  int rank = lu_covar<kM>(jtj, cv, sumsq, n);
 #pragma unroll
   for (int i = 0; i < kM; ++i) sd[i] = sqrt(cv[i * kM + i]);  // misc_core.c:600
   rho[0] = cv[0 * kM + 1] / sqrt(cv[0 * kM + 0] * cv[1 * kM + 1]);  // misc_core.c:610
@@ -141,6 +151,7 @@ __device__ __forceinline__ void finish_fit(const StatsCtx &c, long long r, long 
 #pragma unroll
   for (int k = 0; k < kM * kM; ++k) finite = finite && lm_finite(cv[k]);
   if (!finite) rank = 0;
+  if (RAGGED && n < kM) rank = 0;
   if (rank == 0) {  // what a single fit's covar shows when levmar could not invert J^T J
 #pragma unroll
     for (int k = 0; k < kM * kM; ++k) cv[k] = 0.0;
@@ -154,7 +165,7 @@ __device__ __forceinline__ void finish_fit(const StatsCtx &c, long long r, long 
   if (c.stats) {
     double *o = c.stats + r * kStatsSz;
     o[0] = sumsq;
-    o[1] = 1.0 - sumsq / sstot;  // misc_core.c:657 (the IEEE result when SStot = 0)
+    o[1] = (RAGGED && n <= 0) ? 0.0 : 1.0 - sumsq / sstot;  // misc_core.c:657 (the IEEE result when SStot = 0)
     o[2] = sd[0];
     o[3] = sd[1];
     o[4] = sd[2];
@@ -165,91 +176,14 @@ __device__ __forceinline__ void finish_fit(const StatsCtx &c, long long r, long 
   if (c.rank) c.rank[r] = rank;
 }
 
-// ---- n <= 16: a 16-lane DPP row per fit ----------------------------------------------------------------------
-template <int MODEL, int JAC, bool FAST>
-__global__ __launch_bounds__(kRowsThreads) void fit_stats_rows_kernel(StatsCtx c) {
-  __shared__ double sh[kRowsFits][kRow];
-  const int slot = threadIdx.x >> 4, i = threadIdx.x & 15, lane = threadIdx.x & (kWave - 1);
-  const long long q = fit_of_row(c, (long long)blockIdx.x * kRowsFits + slot);
-  const bool ok = q >= 0 && i < c.n;
-  double acc[kNS], xv = 0.0;
-#pragma unroll
-  for (int k = 0; k < kNS; ++k) acc[k] = 0.0;
-  if (ok) {
-    JacUniforms u;
-    build_uniforms<MODEL, JAC>(c.p + 3 * q, c.delta, u);
-    xv = sample_acc<MODEL, JAC, FAST>(u, c.angles + (size_t)q * 3 * c.n, c.x + (size_t)q * c.n, c.n, i, acc);
-  }
-#pragma unroll
-  for (int k = 0; k < kNS; ++k) acc[k] = row_reduce_to_last<OpSum>(acc[k]);  // lanes beyond n add +0.0
-  const double mean = __shfl(acc[kNS - 1], lane | 15) / (double)c.n;        // misc_core.c:636
-  const double dx = ok ? xv - mean : 0.0;
-  const double st = row_reduce_to_last<OpSum>(dx * dx);
-  if (i == 15) {
-#pragma unroll
-    for (int k = 0; k < kNS; ++k) sh[slot][k] = acc[k];
-    sh[slot][kNS] = st;
-  }
-  __syncthreads();
-  if (threadIdx.x < kRowsFits) {
-    const long long r = (long long)blockIdx.x * kRowsFits + threadIdx.x;
-    const long long qf = fit_of_row(c, r);
-    if (qf >= 0) finish_fit(c, r, qf, sh[threadIdx.x]);
-  }
-}
 
-// ---- n <= 256: a wavefront per fit ---------------------------------------------------------------------------
+// ---- helpers of the wavefront / workgroup kernels ------------------------------------------------------------------------
 __device__ __forceinline__ double wave_last(double v) {  // lane 63's value, in scalar registers
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), kWave - 1);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), kWave - 1);
   return __hiloint2double(hi, lo);
 }
 
-template <int MODEL, int JAC, bool FAST>
-__global__ __launch_bounds__(kWaveThreads) void fit_stats_wave_kernel(StatsCtx c) {
-  __shared__ double sh[kWaveFits][kRow];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & (kWave - 1);
-  const long long q = fit_of_row(c, (long long)blockIdx.x * kWaveFits + wave);  // wave-uniform
-  double acc[kNS], xs[kWavePer];
-#pragma unroll
-  for (int k = 0; k < kNS; ++k) acc[k] = 0.0;
-  if (q >= 0) {
-    JacUniforms u;
-    build_uniforms<MODEL, JAC>(c.p + 3 * q, c.delta, u);
-    u = scalar_copy(u);
-    const double *a = c.angles + (size_t)q * 3 * c.n, *x = c.x + (size_t)q * c.n;
-#pragma unroll
-    for (int k = 0; k < kWavePer; ++k) {
-      const int i = lane + k * kWave;
-      xs[k] = 0.0;
-      if (i < c.n) xs[k] = sample_acc<MODEL, JAC, FAST>(u, a, x, c.n, i, acc);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < kNS; ++k) acc[k] = wave_reduce_to_last<OpSum>(acc[k]);
-  const double mean = wave_last(acc[kNS - 1]) / (double)c.n;
-  double st = 0.0;
-  if (q >= 0) {
-#pragma unroll
-    for (int k = 0; k < kWavePer; ++k)
-      if (lane + k * kWave < c.n) {
-        const double dx = xs[k] - mean;
-        st += dx * dx;
-      }
-  }
-  st = wave_reduce_to_last<OpSum>(st);
-  if (lane == kWave - 1) {
-#pragma unroll
-    for (int k = 0; k < kNS; ++k) sh[wave][k] = acc[k];
-    sh[wave][kNS] = st;
-  }
-  __syncthreads();
-  if (threadIdx.x < kWaveFits) {
-    const long long r = (long long)blockIdx.x * kWaveFits + threadIdx.x;
-    const long long qf = fit_of_row(c, r);
-    if (qf >= 0) finish_fit(c, r, qf, sh[threadIdx.x]);
-  }
-}
 
 // ---- a workgroup's share [first, last) of one fit: the eight sums into out[0..kNS) (LDS, visible to all on return) ---
 template <int MODEL, int JAC, bool FAST>
@@ -276,21 +210,18 @@ __device__ __forceinline__ void block_spread(const StatsCtx &c, long long q, int
   block_reduce<1, kBlockThreads>(st, 0.0, buf, out);
 }
 
-// ---- n <= 4096: a workgroup per fit ----------------------------------------------------------------------------
-template <int MODEL, int JAC, bool FAST>
-__global__ __launch_bounds__(kBlockThreads) void fit_stats_block_kernel(StatsCtx c) {
-  __shared__ double buf[reduce_buf_doubles<kBlockThreads>()];
-  __shared__ double out[kSlots];
-  const long long r = blockIdx.x, q = fit_of_row(c, r);  // workgroup-uniform
-  if (q < 0) return;
-  block_sums<MODEL, JAC, FAST>(c, q, 0, c.n, buf, out);
-  double row[kRow];
-#pragma unroll
-  for (int k = 0; k < kNS; ++k) row[k] = out[k];
-  block_spread(c, q, 0, c.n, row[kNS - 1] / (double)c.n, buf, out);  // (x is read again: the fit's 8 n bytes are in L2)
-  row[kNS] = out[0];
-  if (threadIdx.x == 0) finish_fit(c, r, q, row);
-}
+
+// ---- n <= 16 / 256 / 4096: a 16-lane row / a wavefront / a workgroup per fit; uniform, and with per-fit sample counts -------------
+#define FIT_STATS_KERNEL(kind) fit_stats_##kind##_kernel
+#define FIT_STATS_RAGGED false
+#include "fit_stats_kernels.inc"
+#undef FIT_STATS_KERNEL
+#undef FIT_STATS_RAGGED
+#define FIT_STATS_KERNEL(kind) fit_stats_ragged_##kind##_kernel
+#define FIT_STATS_RAGGED true
+#include "fit_stats_kernels.inc"
+#undef FIT_STATS_KERNEL
+#undef FIT_STATS_RAGGED
 
 // ---- n > 4096: several workgroups per fit, partial rows, a folding kernel --------------------------------------
 template <int MODEL, int JAC, bool FAST>
@@ -336,7 +267,7 @@ __global__ __launch_bounds__(kBlockThreads) void fit_stats_fold_kernel(StatsCtx 
     double row[kRow];
 #pragma unroll
     for (int k = 0; k < kRow; ++k) row[k] = out[k];
-    finish_fit(c, r, q, row);
+    finish_fit(c, r, q, row, c.n);
   }
 }
 
@@ -344,7 +275,7 @@ typedef void (*StatsKernel)(StatsCtx);
 // fast: the prepared-sample variant (exp(n log c) for pow(c, n)), an A/B switch only -- see stats_fast_path().  Ward's two paths
 // perform the same operations (brdf_models.h), so its `fast` entries are the exact kernels.
 template <template <int, int, bool> class K>
-StatsKernel pick(int model, int jac, bool fast) {
+StatsKernel pick1(int model, int jac, bool fast) {
   static const StatsKernel t[2][MODEL_COUNT][3] = {{{K<0, 0, false>::fn, K<0, 1, false>::fn, K<0, 2, false>::fn},
                                                    {K<1, 0, false>::fn, K<1, 1, false>::fn, K<1, 2, false>::fn},
                                                    {K<2, 0, false>::fn, K<2, 1, false>::fn, K<2, 2, false>::fn}},
@@ -365,6 +296,23 @@ template <int M, int J, bool F>
 struct BlockK {
   static constexpr StatsKernel fn = fit_stats_block_kernel<M, J, F>;
 };
+template <int M, int J, bool F>
+struct RowsRaggedK {
+  static constexpr StatsKernel fn = fit_stats_ragged_rows_kernel<M, J, F>;
+};
+template <int M, int J, bool F>
+struct WaveRaggedK {
+  static constexpr StatsKernel fn = fit_stats_ragged_wave_kernel<M, J, F>;
+};
+template <int M, int J, bool F>
+struct BlockRaggedK {
+  static constexpr StatsKernel fn = fit_stats_ragged_block_kernel<M, J, F>;
+};
+// the uniform instance, or with per-fit counts the RAGGED one
+template <template <int, int, bool> class K, template <int, int, bool> class KR>
+StatsKernel pick(int model, int jac, bool fast, bool ragged) {
+  return ragged ? pick1<KR>(model, jac, fast) : pick1<K>(model, jac, fast);
+}
 template <int M, int J, bool F>
 struct PartialK {
   static constexpr StatsKernel fn = fit_stats_partial_kernel<M, J, F>;
@@ -407,8 +355,61 @@ int fit_stats_check(const FitStatsArgs &a, const char *who) {
   return 0;
 }
 
+// ragged statistics of fits with a stride above 4096: one after the other.  A fit of k >= 3 samples is the uniform pass with S = 1,
+// n = k over its three plane prefixes packed next to each other; a refused one (k < 3) takes the ragged workgroup kernel, which
+// reads the first k samples of the row where it lies.
+namespace {
+int stats_launches(const FitStatsArgs &a, const char *who, bool refused_large);
+int stats_of_large_ragged(const FitStatsArgs &a, const char *who) {
+  if (a.d_src) {
+    set_error("%s(): row indirection with per-fit counts is limited to n <= %d", who, kBlockMaxN);
+    return kLmError;
+  }
+  std::vector<int> counts((size_t)a.S);
+  STATS_OK(hipMemcpyAsync(counts.data(), a.d_counts, sizeof(int) * counts.size(), hipMemcpyDeviceToHost, a.stream));
+  STATS_OK(hipStreamSynchronize(a.stream));
+  int kmax = 0;
+  for (int &k : counts) {
+    if (k < 0 || k > a.n) k = 0;
+    if (k > kmax) kmax = k;
+  }
+  DeviceBlock<double> pack;
+  if (kmax >= kM) STATS_OK(pack.ensure(3 * (size_t)kmax));
+  for (int s = 0; s < a.S; ++s) {
+    const int k = counts[s];
+    FitStatsArgs f = a;
+    f.S = 1;
+    f.d_angles = a.d_angles + (size_t)s * 3 * a.n;
+    f.d_x = a.d_x + (size_t)s * a.n;
+    f.d_p = a.d_p + (size_t)s * kM;
+    f.d_covar = a.d_covar ? a.d_covar + (size_t)s * kM * kM : nullptr;
+    f.d_stats = a.d_stats ? a.d_stats + (size_t)s * kStatsSz : nullptr;
+    f.d_rank = a.d_rank ? a.d_rank + s : nullptr;
+    if (k >= kM) {
+      for (int pl = 0; pl < 3; ++pl)
+        STATS_OK(hipMemcpyAsync(pack.ptr + (size_t)pl * k, f.d_angles + (size_t)pl * a.n, sizeof(double) * k, hipMemcpyDeviceToDevice, a.stream));
+      f.d_angles = pack.ptr;
+      f.n = k;
+      f.d_counts = nullptr;
+    } else {
+      f.d_counts = a.d_counts + s;
+    }
+    if (stats_launches(f, who, k < kM) != 0) return kLmError;
+  }
+  STATS_OK(hipStreamSynchronize(a.stream));  // (the packed planes are about to go away)
+  return 0;
+}
+}  // namespace
+
 int fit_stats_enqueue(const FitStatsArgs &a, const char *who) {
   if (fit_stats_check(a, who) != 0) return kLmError;
+  if (a.d_counts && a.n > kBlockMaxN) return stats_of_large_ragged(a, who);
+  return stats_launches(a, who, false);
+}
+
+namespace {
+// refused_large: one fit of fewer than kM samples in rows of a stride above 4096 -- the workgroup kernel, whatever the stride
+int stats_launches(const FitStatsArgs &a, const char *who, bool refused_large) {
   StatsCtx c;
   c.angles = a.d_angles;
   c.x = a.d_x;
@@ -420,6 +421,8 @@ int fit_stats_enqueue(const FitStatsArgs &a, const char *who) {
   c.partials = nullptr;
   c.rows = a.d_src ? a.rows : a.S;
   c.n = a.n;
+  c.counts = a.d_counts;
+  const bool ragged = a.d_counts != nullptr;
   c.chunk = c.nb = 0;
   // "opts==NULL": forward differences with LM_DIFF_DELTA (lmbc_core.c:1088); opts[4] < 0: central, step |opts[4]| (lm_core.c:515-519)
   const double d4 = a.opts ? a.opts[4] : LM_DIFF_DELTA;
@@ -432,12 +435,12 @@ int fit_stats_enqueue(const FitStatsArgs &a, const char *who) {
   (void)hipGetLastError();
   if (a.n <= 16) {
     const long long blocks = (c.rows + kRowsFits - 1) / kRowsFits;
-    hipLaunchKernelGGL(pick<RowsK>(a.model, jac, fast), dim3((unsigned)blocks), dim3(kRowsThreads), 0, a.stream, c);
+    hipLaunchKernelGGL((pick<RowsK, RowsRaggedK>(a.model, jac, fast, ragged)), dim3((unsigned)blocks), dim3(kRowsThreads), 0, a.stream, c);
   } else if (a.n <= kWaveMaxN) {
     const long long blocks = (c.rows + kWaveFits - 1) / kWaveFits;
-    hipLaunchKernelGGL(pick<WaveK>(a.model, jac, fast), dim3((unsigned)blocks), dim3(kWaveThreads), 0, a.stream, c);
-  } else if (a.n <= kBlockMaxN) {
-    hipLaunchKernelGGL(pick<BlockK>(a.model, jac, fast), dim3((unsigned)c.rows), dim3(kBlockThreads), 0, a.stream, c);
+    hipLaunchKernelGGL((pick<WaveK, WaveRaggedK>(a.model, jac, fast, ragged)), dim3((unsigned)blocks), dim3(kWaveThreads), 0, a.stream, c);
+  } else if (a.n <= kBlockMaxN || refused_large) {
+    hipLaunchKernelGGL((pick<BlockK, BlockRaggedK>(a.model, jac, fast, ragged)), dim3((unsigned)c.rows), dim3(kBlockThreads), 0, a.stream, c);
   } else {
     // chunks of a whole number of sweeps of the workgroup, at least 4096 samples, at most kMaxPartials of them per fit
     long long chunk = ((long long)a.n + kMaxPartials - 1) / kMaxPartials;
@@ -453,7 +456,7 @@ int fit_stats_enqueue(const FitStatsArgs &a, const char *who) {
     STATS_OK(hipMallocAsync(&part, sizeof(double) * kRow * (size_t)c.rows * c.nb, a.stream));
     c.partials = static_cast<double *>(part);
     const unsigned grid = (unsigned)(c.rows * c.nb);
-    hipLaunchKernelGGL(pick<PartialK>(a.model, jac, fast), dim3(grid), dim3(kBlockThreads), 0, a.stream, c);
+    hipLaunchKernelGGL(pick1<PartialK>(a.model, jac, fast), dim3(grid), dim3(kBlockThreads), 0, a.stream, c);
     hipLaunchKernelGGL(fit_stats_spread_kernel, dim3(grid), dim3(kBlockThreads), 0, a.stream, c);
     hipLaunchKernelGGL(fit_stats_fold_kernel, dim3((unsigned)c.rows), dim3(kBlockThreads), 0, a.stream, c);
     const hipError_t le = hipGetLastError();
@@ -464,5 +467,6 @@ int fit_stats_enqueue(const FitStatsArgs &a, const char *who) {
   STATS_OK(hipGetLastError());
   return 0;
 }
+}  // namespace
 
 }  // namespace brdf

@@ -61,13 +61,17 @@ __device__ long long g_lane_stamps[16];
 
 // W = waves per SIMD the register allocator plans for (512 / 256 / 128 registers per lane at 1 / 2 / 4); LDS allows
 // 5-6 waves per CU at n = 16.  BRDF_HIP_LANE_WAVES picks the variant (measurements: DESIGN.md section 6).
-template <int MODEL, bool FAST, int W>
-__global__ __launch_bounds__(kWave, W) void lane_fit_kernel(BatchCtx ctx, int *queue) {
+// RAGGED (a second instantiation; the uniform one is the code it was): every lane carries the sample count of its own fit
+// (RaggedBatchCtx::counts), ctx.n being the row stride; the sweeps below run to the lane's count, in the reference's order for that count,
+// and a count below 3 (or outside [0, stride]) is refused at refill as start() refuses n < m.
+template <int MODEL, bool FAST, int W, bool RAGGED = false>
+__global__ __launch_bounds__(kWave, W) void lane_fit_kernel(BatchCtxOf<RAGGED> ctx, int *queue) {
   using Mdl = BrdfModel<MODEL>;
   constexpr int NP = 3 + (Mdl::prep_planes == 2 ? 1 : 0);  // c0, q1, [q2], x
   extern __shared__ double smp[];                          // [n][NP][64]
   const int lane = threadIdx.x;
   const int n = ctx.n;
+  int ncnt = n;  // samples of this lane's fit (RAGGED: set at refill)
   const int S = ctx.S;
   // (locals, not pointers into the by-value ctx: taking its members' addresses parks the whole struct in scratch)
   const double ov[5] = {ctx.opts[0], ctx.opts[1], ctx.opts[2], ctx.opts[3], ctx.opts[4]};
@@ -136,7 +140,8 @@ __global__ __launch_bounds__(kWave, W) void lane_fit_kernel(BatchCtx ctx, int *q
           const double *a = ctx.angles + (size_t)f * 3 * n;
           const double *xs = ctx.x + (size_t)f * n;
           bool bad = false;
-          for (int i = 0; i < n; ++i) {
+          if constexpr (RAGGED) ncnt = ragged_count(ctx.counts, f, n);
+          for (int i = 0; i < ncnt; ++i) {
             const double c0 = a[i];
             const double r1 = Mdl::uses_c1 ? a[n + i] : 0.0;
             const double r2 = Mdl::uses_c2 ? a[2 * n + i] : 0.0;
@@ -152,6 +157,7 @@ __global__ __launch_bounds__(kWave, W) void lane_fit_kernel(BatchCtx ctx, int *q
           if (!(FAST && bad)) {
             const double p0[kM] = {ctx.p[(size_t)f * kM], ctx.p[(size_t)f * kM + 1], ctx.p[(size_t)f * kM + 2]};
             m.begin(p0);
+            if (RAGGED && ncnt < kM) m.h.req.kind = RQ_DONE;  // lmbc_core.c:440-443 for this lane's own count
             if (m.h.req.kind == RQ_DONE) {  // refused by start() (n < m, inconsistent box): lmbc_core.c:440-454
               if (ctx.ret) ctx.ret[f] = kLmError;
               if (ctx.info)
@@ -193,7 +199,7 @@ __global__ __launch_bounds__(kWave, W) void lane_fit_kernel(BatchCtx ctx, int *q
           };
           // two rows per trip (one wave per SIMD: nothing else hides a row's dependent exp chains), accumulated in the
           // reference's order all the same
-          int l = n;
+          int l = ncnt;
           for (; W == 1 && l >= 2; l -= 2) {
             double ea, eb, ja[kM], jb[kM];
             row(l - 1, ea, ja);
@@ -216,7 +222,7 @@ __global__ __launch_bounds__(kWave, W) void lane_fit_kernel(BatchCtx ctx, int *q
         u.n0 = Mdl::nl(r.p);
         u.scal = r.scal;
         if (kind == RQ_SCALED) {  // lmbc_core.c:163-166, descending
-          for (int l = n; l-- > 0;) {
+          for (int l = ncnt; l-- > 0;) {
             const double *d = sp + (size_t)l * NP * kWave;
             const Prep q{d[kWave], NP == 4 ? d[2 * kWave] : 0.0};
             const double t = (d[(NP - 1) * kWave] - model_value<MODEL, FAST>(u, d[0], q)) / u.scal;
@@ -224,7 +230,7 @@ __global__ __launch_bounds__(kWave, W) void lane_fit_kernel(BatchCtx ctx, int *q
           }
         } else {  // RQ_EVAL: misc_core.c:721-807 -- blocks of 8 from the top down, accumulator (top - j) & 3; then the tail upwards
           double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-          const int body = (n >> 3) << 3;
+          const int body = (ncnt >> 3) << 3;
           for (int jb = body - 4; jb >= 0; jb -= 4) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -239,12 +245,12 @@ __global__ __launch_bounds__(kWave, W) void lane_fit_kernel(BatchCtx ctx, int *q
               mx = fmax(mx, fabs(e));
             }
           }
-          for (int t = body; t < n; ++t) {
+          for (int t = body; t < ncnt; ++t) {
             const double *d = sp + (size_t)t * NP * kWave;
             const Prep q{d[kWave], NP == 4 ? d[2 * kWave] : 0.0};
             const double e = d[(NP - 1) * kWave] - model_value<MODEL, FAST>(u, d[0], q);
             const double e2 = e * e;
-            const int k = (7 - (n - t)) & 3;
+            const int k = (7 - (ncnt - t)) & 3;
             a0 += (k == 0) ? e2 : 0.0;
             a1 += (k == 1) ? e2 : 0.0;
             a2 += (k == 2) ? e2 : 0.0;
@@ -286,22 +292,24 @@ __global__ __launch_bounds__(kWave, W) void lane_fit_kernel(BatchCtx ctx, int *q
 }
 
 namespace {
-using LaneFn = void (*)(BatchCtx, int *);
-template <int W>
-LaneFn lane_kernel_w(int model, bool fast) {
-  static const LaneFn table[2][MODEL_COUNT] = {
-      {lane_fit_kernel<0, false, W>, lane_fit_kernel<1, false, W>, nullptr},  // Ward's prepared path has no domain restriction
-      {lane_fit_kernel<0, true, W>, lane_fit_kernel<1, true, W>, lane_fit_kernel<2, true, W>},
+template <bool R>
+using LaneFn = void (*)(BatchCtxOf<R>, int *);
+template <int W, bool R>
+LaneFn<R> lane_kernel_w(int model, bool fast) {
+  static const LaneFn<R> table[2][MODEL_COUNT] = {
+      {lane_fit_kernel<0, false, W, R>, lane_fit_kernel<1, false, W, R>, nullptr},  // Ward's prepared path has no domain restriction
+      {lane_fit_kernel<0, true, W, R>, lane_fit_kernel<1, true, W, R>, lane_fit_kernel<2, true, W, R>},
   };
   return table[fast ? 1 : 0][model];
 }
-LaneFn lane_kernel(int model, bool fast, int w) {
-  return w == 1 ? lane_kernel_w<1>(model, fast) : (w == 4 ? lane_kernel_w<4>(model, fast) : lane_kernel_w<2>(model, fast));
+template <bool R>
+LaneFn<R> lane_kernel(int model, bool fast, int w) {
+  return w == 1 ? lane_kernel_w<1, R>(model, fast) : (w == 4 ? lane_kernel_w<4, R>(model, fast) : lane_kernel_w<2, R>(model, fast));
 }
 }  // namespace
 
 // dlevmar_bc_dif, n <= kLaneMaxN.  c.flags: S ints; queue: 2 ints, zeroed by the caller on `stream`.
-int lane_fit_enqueue(int model, bool fast, const BatchCtx &c, int *queue, hipStream_t stream) {
+int lane_fit_enqueue(int model, bool fast, const BatchCtx &c, const int *counts, int *queue, hipStream_t stream) {
   int dev = 0;
   HIP_OK(hipGetDevice(&dev));
   int cus = 0;
@@ -320,7 +328,10 @@ int lane_fit_enqueue(int model, bool fast, const BatchCtx &c, int *queue, hipStr
   if (waves > need) waves = need;
   // (a launch over an empty set costs one queue sweep: every lane's first fetch finds no marked fit)
   return launch_fast_then_exact(fast, model != MODEL_WARD, c.flags, (size_t)c.S, queue, stream, [&](bool fast_kernel, int *q) {
-    hipLaunchKernelGGL(lane_kernel(model, fast_kernel, w), dim3((unsigned)waves), dim3(kWave), lds, stream, cc, q);
+    if (counts)
+      hipLaunchKernelGGL(lane_kernel<true>(model, fast_kernel, w), dim3((unsigned)waves), dim3(kWave), lds, stream, ragged_ctx(cc, counts), q);
+    else
+      hipLaunchKernelGGL(lane_kernel<false>(model, fast_kernel, w), dim3((unsigned)waves), dim3(kWave), lds, stream, cc, q);
   });
 }
 

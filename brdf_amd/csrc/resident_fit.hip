@@ -151,14 +151,17 @@ int resident_fit_last_trace(long long *out, int max_rows) {
   return rows;
 }
 
-int resident_batch_enqueue(int model, int method, bool fast, const BatchCtx &c, hipStream_t stream) {
+int resident_batch_enqueue(int model, int method, bool fast, const BatchCtx &c, const int *counts, hipStream_t stream) {
   if (!kKernels[model][method]) {
     set_error("resident kernels of model %d / method %d are not in this build", model, method);
     return kLmError;
   }
   const ResidentKernels k = kKernels[model][method]();
   return launch_fast_then_exact(fast, k.batched[kExactPath] != nullptr, c.flags, (size_t)c.S, nullptr, stream, [&](bool fast_kernel, int *) {
-    hipLaunchKernelGGL(k.batched[fast_kernel ? kFastPath : kExactPath], dim3(c.S), dim3(kRThreads), 0, stream, ResidentCtx{}, c);
+    if (counts)  // per-fit sample counts: the RAGGED instances
+      hipLaunchKernelGGL(k.ragged[fast_kernel ? kFastPath : kExactPath], dim3(c.S), dim3(kRThreads), 0, stream, ResidentCtx{}, ragged_ctx(c, counts));
+    else
+      hipLaunchKernelGGL(k.batched[fast_kernel ? kFastPath : kExactPath], dim3(c.S), dim3(kRThreads), 0, stream, ResidentCtx{}, c);
   });
 }
 

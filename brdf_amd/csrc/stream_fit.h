@@ -109,11 +109,19 @@ int cosines_run(const double *d_vertices, const int *d_faces, const double *d_no
                 const double *leds, int L, const double *view, int rv_mode, double *d_angles, hipStream_t stream);
 void led_table(double *out16x3);
 // the pixel loop of CalcBRDFEquation (capture_fit.hip)
+// the validity rule of brdf_hip_fit_capture_masked_dev: sample i of a fit takes part iff v_min <= 8-bit intensity <= v_max and every
+// cosine plane the model reads is > cos_min; d_surface_count[nf][3] (device, or null) receives the stored fits' sample counts
+struct CaptureMask {
+  int v_min, v_max;
+  double cos_min;
+  int *d_surface_count;
+};
 int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
                     const double *d_vertices, const int *d_faces, const double *d_normals, int nf, const double *leds,
                     const double *view, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
                     const double *opts, double *d_brdf_surfaces, double *avg, long long *n_pixels, hipStream_t stream,
-                    double *d_surface_covar = nullptr, double *d_surface_stats = nullptr, int *d_surface_rank = nullptr);  // the optional statistics tail
+                    double *d_surface_covar = nullptr, double *d_surface_stats = nullptr, int *d_surface_rank = nullptr,  // the optional statistics tail
+                    const CaptureMask *mask = nullptr);  // brdf_hip_fit_capture_masked_dev: a validity rule, a ragged fit
 
 // one model evaluation / analytic Jacobian over n samples (stream_fit.hip): d_hx [n], d_jac [n][3]
 int model_eval_run(int model, const double *d_angles, int n, const double *p, double *d_hx, hipStream_t stream);

@@ -123,8 +123,42 @@ def last_channels_stats(channels: int = 3):
     return {"shared_launch": bool(shared.value), "channels": per, "kernel_us": lib.brdf_hip_last_channels_kernel_us()}
 
 
-def fit_batch(method: int, model: int, angles, x, p0, *, lb=None, ub=None, itmax=100, opts=None):
+def compact_samples(angles, x, valid):
+    """Stable front-compaction of the valid samples of S fits: angles [S,3,n], x [S,n], valid [S,n] (bool) -> (angles, x, counts)
+    of the same shapes and kind (torch tensors on the inputs' device, or numpy arrays), counts [S] int32.  Fit s's valid samples,
+    in their order, are its samples [0, counts[s]); the entries behind them are NaN (a ragged fit never uses them).  What
+    fit_capture_masked does on the device, for callers that build their own batches: fit_batch(..., counts=counts)."""
+    if isinstance(x, np.ndarray):
+        valid = np.asarray(valid, dtype=bool)
+        _require(x.ndim == 2 and angles.shape == (x.shape[0], 3, x.shape[1]) and valid.shape == x.shape, "angles [S,3,n], x [S,n], valid [S,n]")
+        order = np.argsort(~valid, axis=1, kind="stable")  # valid samples first, each group in its own order
+        counts = valid.sum(axis=1).astype(np.int32)
+        keep = np.arange(x.shape[1])[None, :] < counts[:, None]
+        xo = np.where(keep, np.take_along_axis(x, order, axis=1), np.nan)
+        ao = np.where(keep[:, None, :], np.take_along_axis(angles, np.broadcast_to(order[:, None, :], angles.shape), axis=2), np.nan)
+        return ao, xo, counts
+    import torch
+    valid = valid.to(torch.bool)
+    _require(x.dim() == 2 and tuple(angles.shape) == (x.shape[0], 3, x.shape[1]) and valid.shape == x.shape, "angles [S,3,n], x [S,n], valid [S,n]")
+    order = torch.sort((~valid).to(torch.int8), dim=1, stable=True).indices
+    counts = valid.sum(dim=1).to(torch.int32)
+    keep = torch.arange(x.shape[1], device=x.device)[None, :] < counts[:, None]
+    nan = torch.full((), float("nan"), dtype=x.dtype, device=x.device)
+    xo = torch.where(keep, torch.gather(x, 1, order), nan)
+    ao = torch.where(keep[:, None, :], torch.gather(angles, 2, order[:, None, :].expand(angles.shape)), nan)
+    return ao, xo, counts
+
+
+def _counts_arg(counts, S, device, torch):
+    _require(counts.is_cuda and counts.device == device and counts.dtype == torch.int32 and tuple(counts.shape) == (S,),
+             "counts: CUDA int32 [S] on the device of x")
+    return counts.contiguous()
+
+
+def fit_batch(method: int, model: int, angles, x, p0, *, lb=None, ub=None, itmax=100, opts=None, counts=None):
     """S independent fits.  angles: CUDA float64 [S,3,n], x: [S,n], p0: CUDA float64 [S,3] (updated in place).
+    counts (CUDA int32 [S], optional): a ragged batch -- fit s uses samples [0, counts[s]) of its rows, n is the row stride
+    (brdf_hip_fit_batch_ragged_dev: a count below 3 gives ret -1, zero info, p as it came; bucket very unequal counts by size class).
 
     Returns (p [S,3], info [S,10], ret [S] int32) as CUDA tensors; asynchronous on the current stream.
     """
@@ -139,6 +173,15 @@ def fit_batch(method: int, model: int, angles, x, p0, *, lb=None, ub=None, itmax
     info = torch.zeros((S, 10), dtype=torch.float64, device=x.device)
     ret = torch.zeros((S,), dtype=torch.int32, device=x.device)
     lb_a, ub_a, op_a = _f64(lb, 3), _f64(ub, 3), _f64(opts, 5)
+    if counts is not None:
+        counts = _counts_arg(counts, S, x.device, torch)
+        with torch.cuda.device(x.device):
+            rc = lib.brdf_hip_fit_batch_ragged_dev(method, model, angles.data_ptr(), x.data_ptr(), counts.data_ptr(), S, n, p.data_ptr(),
+                                                   _dptr(lb_a), _dptr(ub_a), itmax, _dptr(op_a), info.data_ptr(), ret.data_ptr(),
+                                                   _stream_handle(torch))
+        if rc != 0:
+            raise RuntimeError(f"brdf_hip_fit_batch_ragged_dev failed: {last_error()}")
+        return p, info, ret
     with torch.cuda.device(x.device):
         rc = lib.brdf_hip_fit_batch_dev(method, model, angles.data_ptr(), x.data_ptr(), S, n, p.data_ptr(), _dptr(lb_a),
                                         _dptr(ub_a), itmax, _dptr(op_a), info.data_ptr(), ret.data_ptr(),
@@ -156,11 +199,13 @@ class FitStats:
     rank: object   # [S] int32: 3, or 0 where the covariance could not be formed (covar and its six derived values are 0)
 
 
-def fit_stats_batch(method: int, model: int, angles, x, p, *, opts=None) -> FitStats:
+def fit_stats_batch(method: int, model: int, angles, x, p, *, opts=None, counts=None) -> FitStats:
     """Covariance, standard errors, correlations and R^2 of S fits at their fitted points p: one evaluation pass, whoever
     fitted p.  angles [S,3,n], x [S,n], p [S,3]: CUDA float64 tensors (asynchronous on the current stream), or numpy arrays
     (host-pointer entry: uploads, runs, downloads).  `method` selects how the Jacobian row is formed (finite differences
-    with opts[4]'s step, or the analytic row); for METHOD_DIF it is the Jacobian at p, not levmar's secant one."""
+    with opts[4]'s step, or the analytic row); for METHOD_DIF it is the Jacobian at p, not levmar's secant one.
+    counts ([S] int32, of the inputs' kind; optional): per-fit sample counts of a ragged batch (degrees of freedom counts[s] - 3;
+    below 3: rank 0)."""
     op_a = _f64(opts, 5)
     if isinstance(x, np.ndarray):
         angles = np.ascontiguousarray(angles, dtype=np.float64)
@@ -170,6 +215,14 @@ def fit_stats_batch(method: int, model: int, angles, x, p, *, opts=None) -> FitS
         S, n = x.shape
         _require(angles.shape == (S, 3, n) and p.shape == (S, 3), "angles must be [S, 3, n], p [S, 3]")
         covar, stats, rank = np.zeros((S, 3, 3)), np.zeros((S, 8)), np.zeros(S, dtype=np.int32)
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.int32)
+            _require(counts.shape == (S,), "counts must be [S]")
+            rc = lib.brdf_hip_fit_stats_batch_ragged(method, model, _dptr(angles), _dptr(x), counts.ctypes.data_as(C.POINTER(C.c_int)), S, n,
+                                                     _dptr(p), _dptr(op_a), _dptr(covar), _dptr(stats), rank.ctypes.data_as(C.POINTER(C.c_int)))
+            if rc != 0:
+                raise RuntimeError(f"brdf_hip_fit_stats_batch_ragged failed: {last_error()}")
+            return FitStats(covar, stats, rank)
         rc = lib.brdf_hip_fit_stats_batch(method, model, _dptr(angles), _dptr(x), S, n, _dptr(p), _dptr(op_a), _dptr(covar),
                                           _dptr(stats), rank.ctypes.data_as(C.POINTER(C.c_int)))
         if rc != 0:
@@ -185,6 +238,14 @@ def fit_stats_batch(method: int, model: int, angles, x, p, *, opts=None) -> FitS
     covar = torch.zeros((S, 3, 3), dtype=torch.float64, device=x.device)
     stats = torch.zeros((S, 8), dtype=torch.float64, device=x.device)
     rank = torch.zeros((S,), dtype=torch.int32, device=x.device)
+    if counts is not None:
+        counts = _counts_arg(counts, S, x.device, torch)
+        with torch.cuda.device(x.device):
+            rc = lib.brdf_hip_fit_stats_batch_ragged_dev(method, model, angles.data_ptr(), x.data_ptr(), counts.data_ptr(), S, n, p.data_ptr(),
+                                                         _dptr(op_a), covar.data_ptr(), stats.data_ptr(), rank.data_ptr(), _stream_handle(torch))
+        if rc != 0:
+            raise RuntimeError(f"brdf_hip_fit_stats_batch_ragged_dev failed: {last_error()}")
+        return FitStats(covar, stats, rank)
     with torch.cuda.device(x.device):
         rc = lib.brdf_hip_fit_stats_batch_dev(method, model, angles.data_ptr(), x.data_ptr(), S, n, p.data_ptr(), _dptr(op_a),
                                               covar.data_ptr(), stats.data_ptr(), rank.data_ptr(), _stream_handle(torch))
@@ -293,9 +354,28 @@ def cosines(vertices, faces, face_normals, leds, view_origin, *, surfels=None, r
     return out
 
 
+def fit_capture_masked(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, v_min: int = 0, v_max: int = 255,
+                       cos_min: float = -2.0, surface_count=None, **kwargs):
+    """fit_capture(want_stats=True) with a validity rule (brdf_hip_fit_capture_masked_dev): light i of a (pixel, channel) fit takes
+    part iff v_min <= its 8-bit intensity <= v_max and every cosine plane the model reads is > cos_min; the fit is levmar on the
+    valid samples alone (a ragged fit).  The defaults switch both tests off: then every output is bit-identical to fit_capture's.
+    Returns (brdf_surfaces, avg, pixels, FitStats, surface_count [nf,3] int32 CUDA: the sample count of each stored fit; a fit of
+    fewer than 3 samples is refused and leaves p0 in brdf_surfaces).  Keyword arguments as fit_capture."""
+    import torch
+    nf = int(faces.shape[0])
+    if surface_count is None:
+        surface_count = torch.zeros((nf, 3), dtype=torch.int32, device=images.device)
+    _require(surface_count.is_cuda and surface_count.dtype == torch.int32 and tuple(surface_count.shape) == (nf, 3) and surface_count.is_contiguous(),
+             "surface_count: contiguous CUDA int32 [nf,3]")
+    kwargs["want_stats"] = True
+    out = fit_capture(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin,
+                      _mask=(int(v_min), int(v_max), float(cos_min), surface_count), **kwargs)
+    return (*out, surface_count)
+
+
 def fit_capture(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, rv_mode: int = 0,
                 p0=(0.5, 1.0, 1.0), lb=(0.0, 0.0, 0.0), ub=(100.0, 100.0, 100.0), itmax: int = 100, opts=None, brdf_surfaces=None,
-                validate: bool = True, want_stats: bool = False, surface_stats: FitStats | None = None):
+                validate: bool = True, want_stats: bool = False, surface_stats: FitStats | None = None, _mask=None):
     """The pixel loop of CBRDFdata::CalcBRDFEquation (brdfdata.cpp:1188-1227) on the device.  images: CUDA uint8
     [L,H,W,3] (BGR), pixel_map: CUDA int32 [H,W] (face index or -1), mesh as in cosines().  Returns (brdf_surfaces
     CUDA float64 [nf,3,3] = {kd,ks,n} per face and channel, avg[3], number of pixels that carried a face).
@@ -343,6 +423,13 @@ def fit_capture(model: int, images, pixel_map, vertices, faces, face_normals, le
              "surface_stats: float64 covar and stats, int32 rank")
     _require(st.covar.is_contiguous() and st.stats.is_contiguous() and st.rank.is_contiguous() and st.covar.is_cuda and st.stats.is_cuda
              and st.rank.is_cuda, "surface_stats: contiguous CUDA tensors")
+    if _mask is not None:  # fit_capture_masked
+        with torch.cuda.device(images.device):
+            rc = lib.brdf_hip_fit_capture_masked_dev(*args, _stream_handle(torch), st.covar.data_ptr(), st.stats.data_ptr(), st.rank.data_ptr(),
+                                                     _mask[0], _mask[1], _mask[2], _mask[3].data_ptr())
+        if rc != 0:
+            raise RuntimeError(f"brdf_hip_fit_capture_masked_dev failed: {last_error()}")
+        return brdf_surfaces, avg, npx.value, st
     with torch.cuda.device(images.device):
         rc = lib.brdf_hip_fit_capture_stats_dev(*args, _stream_handle(torch), st.covar.data_ptr(), st.stats.data_ptr(), st.rank.data_ptr())
     if rc != 0:

@@ -250,6 +250,43 @@ int brdf_hip_fit_stats_batch_dev(int method, int model, const double *d_angles, 
 int brdf_hip_fit_stats_batch(int method, int model, const double *angles, const double *x, int S, int n, const double *p,
                              const double *opts, double *covar, double *stats, int *rank);
 
+/* ---- per-fit sample counts ("ragged" batches; extensions) ------------------------------------------------- */
+/* brdf_hip_fit_batch_dev / brdf_hip_fit_stats_batch_dev for fits that do not all have n samples: fit s of a ragged batch is levmar
+ * on the first counts[s] samples of its rows.  Leaving samples out of a fit (lights behind the surface, clipped pixels; see
+ * brdf_amd.compact_samples and brdf_hip_fit_capture_masked_dev) is a fit of fewer samples.
+ *   Layout      the uniform call's: d_angles[S][3][n], d_x[S][n]; n is the row stride and the largest count; d_counts[S] is a
+ *               DEVICE array of ints (HOST in the two host-pointer entries).
+ *   Samples     fit s uses samples [0, counts[s]) of each of its rows.
+ *   Padding     entries at or behind counts[s] are never used: they may hold anything, NaN included, and no result depends on them.
+ *   No counts   d_counts == NULL behaves exactly as the uniform entry point (it is that call).
+ *   Too few     0 <= counts[s] < 3 is levmar's own n < m refusal (lm_core.c:502, lmbc_core.c:440): ret[s] = LM_ERROR, info[s] all
+ *               zeros, p[s] as it came -- what the kernels do for any refused start.
+ *   Out of range  a count < 0 or > n is treated the same way (the host cannot see it; nothing outside the row is read).
+ *   Statistics  degrees of freedom are counts[s] - 3 and all sums run over the fit's own samples.  counts[s] < 3 or outside [0, n]:
+ *               rank = 0, zero covar and zeros for the six values derived from it; sumsq and R2 are still written over the samples
+ *               there are (both 0 for a count of 0 or out of range).
+ *   Kernel      chosen by the stride n, as in the uniform calls: a batch whose counts span several size classes (<= 16, 64, 256,
+ *               1024, 4096) runs EVERY fit in the stride's class -- a fit of 5 samples in rows of 4096 occupies a whole workgroup.
+ *               Callers with very unequal counts should bucket their fits by size class and make one call per class.  Within the
+ *               stride's own class a fit's p / info / ret (and covar / stats / rank) are bit-identical to the uniform call with
+ *               n = counts[s] on that fit alone; below it they agree as two summation orders do.
+ *   n > 4096    the fits run one after the other through the single-fit regimes with n = counts[s] (the counts are copied to the
+ *               host next to p; a count below 3 is refused there without a launch); the statistics run the uniform pass per fit
+ *               with S = 1, n = counts[s].  Both synchronise the stream.
+ *   Checks      everything the host can see (null pointers, S or n <= 0, unknown model / method, lb > ub) is checked before any
+ *               HIP call.
+ * Not covered: per-sample weights (a different definition: levmar on sqrt(w) f), dscl, brdf_hip_fit_batch_multi. */
+int brdf_hip_fit_batch_ragged_dev(int method, int model, const double *d_angles, const double *d_x, const int *d_counts, int S, int n,
+                                  double *d_p, const double *lb, const double *ub, int itmax, const double *opts, double *d_info,
+                                  int *d_ret, void *stream);
+int brdf_hip_fit_batch_ragged(int method, int model, const double *angles, const double *x, const int *counts, int S, int n, double *p,
+                              const double *lb, const double *ub, int itmax, const double *opts, double *info, int *ret);
+int brdf_hip_fit_stats_batch_ragged_dev(int method, int model, const double *d_angles, const double *d_x, const int *d_counts, int S,
+                                        int n, const double *d_p, const double *opts, double *d_covar, double *d_stats, int *d_rank,
+                                        void *stream);
+int brdf_hip_fit_stats_batch_ragged(int method, int model, const double *angles, const double *x, const int *counts, int S, int n,
+                                    const double *p, const double *opts, double *covar, double *stats, int *rank);
+
 /* hx[i] = model(p; sample i) for device-resident planes; d_hx DEVICE pointer, p HOST pointer. */
 int brdf_hip_model_eval_dev(int model, const double *d_angles, int n, const double *p, double *d_hx,
                             void *stream);
@@ -307,6 +344,27 @@ int brdf_hip_fit_capture_stats_dev(int model, const unsigned char *d_images, int
                                    const double *lb, const double *ub, int itmax, const double *opts, double *d_brdf_surfaces,
                                    double *avg, long long *n_pixels, void *stream, double *d_surface_covar,
                                    double *d_surface_stats, int *d_surface_rank);
+
+/* brdf_hip_fit_capture_stats_dev with a validity rule: sample i (light i) of fit q = 3 pixel + channel takes part iff
+ *   v_min <= value <= v_max, value being the 8-bit intensity image_i(H-1-y, x)[channel], AND
+ *   every cosine plane the model reads is > cos_min: cos(L.N) always; cos(N.H) for Blinn-Phong and Ward; the third plane
+ *   (cos(R.V) / cos(N.V)) for Phong and Ward.
+ * v_min = 0, v_max = 255 switches the intensity test off, any cos_min < -1 the cosine test.  A fit's valid samples are moved to the
+ * front of its rows, stably in light order (one more kernel behind the gather and the cosines), and the fits run as
+ * brdf_hip_fit_batch_ragged_dev with these counts; the statistics tail is the ragged statistics pass.
+ *   d_surface_count[nf][3] (DEVICE, may be NULL): the sample count of the fit whose result was stored for the face and channel;
+ *   faces no pixel carries are left untouched.  A fit refused for count < 3 leaves p0 in d_brdf_surfaces, as any failed fit does:
+ *   the count map is how the caller tells.
+ * With both conditions off, d_brdf_surfaces, avg, n_pixels and the three statistics maps are bit-identical to
+ * brdf_hip_fit_capture_stats_dev.  Returns LM_ERROR for v_min > v_max as for the other bad arguments, before any HIP call.
+ * Not covered: brdf_hip_fit_capture_single_dev (masking there changes one big fit's n) and the multi-GPU batch. */
+int brdf_hip_fit_capture_masked_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                    const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf,
+                                    const double *leds, const double *view_origin, int rv_mode, const double *p0,
+                                    const double *lb, const double *ub, int itmax, const double *opts, double *d_brdf_surfaces,
+                                    double *avg, long long *n_pixels, void *stream, double *d_surface_covar,
+                                    double *d_surface_stats, int *d_surface_rank, int v_min, int v_max, double cos_min,
+                                    int *d_surface_count);
 
 /* Replaces CBRDFdata::CalcBRDFEquation_SingleBRDF (brdfdata.cpp:1138-1186) with SolveEquation_SingleBRDF (:992-1062): ONE
  * {kd, ks, n} per colour channel for the whole object, fitted with dlevmar_bc_dif to the L samples of every face the pixel
