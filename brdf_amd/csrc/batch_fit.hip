@@ -16,6 +16,7 @@
 #include "../../include/brdf_levmar.h"
 #include "batch_fit.h"
 #include "fit_host.h"
+#include "packed_plan.h"
 
 namespace brdf {
 
@@ -583,7 +584,7 @@ struct Geometry {
 // (measured and rejected for 1024 < n <= 4096, bc_dif: 256 threads x 16 samples per lane to get two workgroups per
 // CU -- the fully unrolled 16-sample sweep spills ~1.2 KB per lane and runs 2x slower than 512 x 8)
 // one wavefront per fit up to 256 samples, one workgroup per fit up to 4096
-bool geometry_for(int n, Geometry *g) {
+constexpr bool geometry_for(int n, Geometry *g) {
   if (n <= 64) *g = {64, 1};
   else if (n <= 256) *g = {64, 4};
   else if (n <= 1024) *g = {256, 4};
@@ -591,6 +592,23 @@ bool geometry_for(int n, Geometry *g) {
   else return false;
   return true;
 }
+// packed_plan.h's size classes are these kernels': a class never spans two geometries, and packed_class() steps exactly where the
+// geometry does, where the lane-per-fit / rows kernels end (kLaneMaxN, kRowLanes) and where the batched kernels end altogether
+constexpr int geometry_id(int n) {
+  Geometry g = {0, 0};
+  return geometry_for(n, &g) ? g.threads * 16 + g.spt : -1;
+}
+constexpr bool packed_classes_agree() {
+  if (packed_bound(0) != kLaneMaxN || packed_bound(0) != kRowLanes || geometry_id(packed_bound(kPackedLargeClass - 1) + 1) != -1) return false;
+  for (int c = 0; c < kPackedLargeClass; ++c) {
+    const int lo = c ? packed_bound(c - 1) + 1 : 1, hi = packed_bound(c);
+    if (packed_class(lo) != c || packed_class(hi) != c || packed_class(hi + 1) != c + 1) return false;
+    if (geometry_id(lo) != geometry_id(hi) || geometry_id(hi) < 0) return false;
+    if (c >= 1 && geometry_id(hi) == geometry_id(hi + 1)) return false;
+  }
+  return packed_class(0) == 0;
+}
+static_assert(packed_classes_agree(), "packed_plan.h: the size classes of a packed batch are the batched kernels' own");
 
 template <bool R>
 BatchFn<R> kernel_for(const Geometry &g, int model, int method, bool fast) {

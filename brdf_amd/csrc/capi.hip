@@ -11,12 +11,14 @@
 #include <mutex>
 
 #include <cfloat>
+#include <climits>
 #include <vector>
 
 #include "../../include/brdf_levmar.h"
 #include "batch_fit.h"
 #include "fit_host.h"
 #include "fit_stats.h"
+#include "packed_fit.h"
 
 using namespace brdf;
 
@@ -667,6 +669,144 @@ int brdf_hip_fit_stats_batch(int method, int model, const double *angles, const 
 int brdf_hip_fit_stats_batch_ragged(int method, int model, const double *angles, const double *x, const int *counts, int S, int n,
                                     const double *p, const double *opts, double *covar, double *stats, int *rank) {
   return fit_stats_host("brdf_hip_fit_stats_batch_ragged", method, model, angles, x, counts, S, n, p, opts, covar, stats, rank);
+}
+
+/* ---- packed batches (packed_fit.hip) ---------------------------------------------------------------------------------------- */
+int brdf_hip_fit_batch_packed_dev(int method, int model, const double *d_angles, const double *d_x, const long long *d_offsets, int S,
+                                  double *d_p, const double *lb, const double *ub, int itmax, const double *opts, double *d_info, int *d_ret,
+                                  long long workspace_bytes, void *stream) {
+  const PackedFitArgs a = {method, model, d_angles, d_x, d_offsets, S, d_p, lb, ub, itmax, opts, d_info, d_ret, workspace_bytes,
+                           static_cast<hipStream_t>(stream)};
+  return packed_fit_run(a, "brdf_hip_fit_batch_packed_dev");
+}
+
+int brdf_hip_fit_stats_batch_packed_dev(int method, int model, const double *d_angles, const double *d_x, const long long *d_offsets, int S,
+                                        const double *d_p, const double *opts, double *d_covar, double *d_stats, int *d_rank,
+                                        long long workspace_bytes, void *stream) {
+  const PackedStatsArgs a = {method, model, d_angles, d_x, d_offsets, S, d_p, opts, d_covar, d_stats, d_rank, workspace_bytes,
+                             static_cast<hipStream_t>(stream)};
+  return packed_stats_run(a, "brdf_hip_fit_stats_batch_packed_dev");
+}
+
+namespace {
+// what the host can see of host offsets (after the entry's own argument check): they must not decrease, and no fit has more than INT_MAX samples
+int check_host_offsets(const char *who, const long long *offsets, int S) {
+  for (int s = 0; s < S; ++s) {
+    if (offsets[s + 1] < offsets[s]) {
+      set_error("%s(): offsets decrease at fit %d (%lld after %lld)", who, s, offsets[s + 1], offsets[s]);
+      return LM_ERROR;
+    }
+    if (offsets[s + 1] - offsets[s] > INT_MAX) {
+      set_error("%s(): fit %d has %lld samples, more than INT_MAX", who, s, offsets[s + 1] - offsets[s]);
+      return LM_ERROR;
+    }
+  }
+  return 0;
+}
+
+// the samples [offsets[0], offsets[S]) and the offsets, rebased to 0, on the device
+struct PackedUpload {
+  DevBuf angles, x, offsets;
+  const long long *d_offsets() const { return reinterpret_cast<const long long *>(offsets.ptr); }
+};
+int upload_packed(const char *who, const double *angles, const double *x, const long long *offsets, int S, PackedUpload *u) {
+  const size_t total = (size_t)(offsets[S] - offsets[0]);
+  if (alloc_doubles(u->angles, 3 * total + 1) || alloc_doubles(u->x, total + 1) || alloc_doubles(u->offsets, (size_t)S + 1)) return LM_ERROR;
+  std::vector<long long> rebased((size_t)S + 1);
+  for (int s = 0; s <= S; ++s) rebased[s] = offsets[s] - offsets[0];
+  hipError_t e = hipMemcpy(u->offsets.ptr, rebased.data(), sizeof(long long) * rebased.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess && total) e = hipMemcpy(u->angles.ptr, angles + 3 * offsets[0], sizeof(double) * 3 * total, hipMemcpyHostToDevice);
+  if (e == hipSuccess && total) e = hipMemcpy(u->x.ptr, x + offsets[0], sizeof(double) * total, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    set_error("%s(): host->device copy failed: %s", who, hipGetErrorString(e));
+    return LM_ERROR;
+  }
+  return 0;
+}
+static_assert(sizeof(long long) == sizeof(double), "the offsets travel in a block of doubles");
+}  // namespace
+
+int brdf_hip_fit_batch_packed(int method, int model, const double *angles, const double *x, const long long *offsets, int S, double *p,
+                              const double *lb, const double *ub, int itmax, const double *opts, double *info, int *ret,
+                              long long workspace_bytes) {
+  const char *who = "brdf_hip_fit_batch_packed";
+  PackedFitArgs a = {method, model, angles, x, offsets, S, p, lb, ub, itmax, opts, nullptr, nullptr, workspace_bytes, nullptr};  // (host pointers: checked for null only)
+  if (packed_fit_check(a, who) != 0 || check_host_offsets(who, offsets, S) != 0) return LM_ERROR;
+  PackedUpload u;
+  DevBuf d_p, d_info, d_ret;
+  if (upload_packed(who, angles, x, offsets, S, &u) != 0 || alloc_doubles(d_p, 3 * (size_t)S) || alloc_doubles(d_info, 10 * (size_t)S) ||
+      alloc_doubles(d_ret, ((size_t)S + 1) / 2 + 1))
+    return LM_ERROR;
+  hipError_t e = hipMemcpy(d_p.ptr, p, sizeof(double) * 3 * S, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    set_error("%s(): host->device copy failed: %s", who, hipGetErrorString(e));
+    return LM_ERROR;
+  }
+  a.d_angles = u.angles.ptr;
+  a.d_x = u.x.ptr;
+  a.d_offsets = u.d_offsets();
+  a.d_p = d_p.ptr;
+  a.d_info = d_info.ptr;
+  a.d_ret = reinterpret_cast<int *>(d_ret.ptr);
+  if (packed_fit_run(a, who) != 0) return LM_ERROR;
+  std::vector<int> host_ret((size_t)S);
+  e = hipStreamSynchronize(nullptr);
+  if (e == hipSuccess) e = hipMemcpy(p, d_p.ptr, sizeof(double) * 3 * S, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && info) e = hipMemcpy(info, d_info.ptr, sizeof(double) * 10 * S, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(host_ret.data(), a.d_ret, sizeof(int) * S, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    set_error("%s(): %s", who, hipGetErrorString(e));
+    return LM_ERROR;
+  }
+  int bad = 0;
+  for (int s = 0; s < S; ++s) {
+    bad += host_ret[s] < 0;
+    if (ret) ret[s] = host_ret[s];
+  }
+  return bad;
+}
+
+int brdf_hip_fit_stats_batch_packed(int method, int model, const double *angles, const double *x, const long long *offsets, int S,
+                                    const double *p, const double *opts, double *covar, double *stats, int *rank, long long workspace_bytes) {
+  const char *who = "brdf_hip_fit_stats_batch_packed";
+  PackedStatsArgs a = {method, model, angles, x, offsets, S, p, opts, covar, stats, rank, workspace_bytes, nullptr};  // (host pointers: checked for null only)
+  if (packed_stats_check(a, who) != 0 || check_host_offsets(who, offsets, S) != 0) return LM_ERROR;
+  PackedUpload u;
+  DevBuf d_p, d_covar, d_stats, d_rank;
+  if (upload_packed(who, angles, x, offsets, S, &u) != 0 || alloc_doubles(d_p, 3 * (size_t)S) || (covar && alloc_doubles(d_covar, 9 * (size_t)S)) ||
+      (stats && alloc_doubles(d_stats, BRDF_STATS_SZ * (size_t)S)) || (rank && alloc_doubles(d_rank, ((size_t)S + 1) / 2 + 1)))
+    return LM_ERROR;
+  hipError_t e = hipMemcpy(d_p.ptr, p, sizeof(double) * 3 * S, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    set_error("%s(): host->device copy failed: %s", who, hipGetErrorString(e));
+    return LM_ERROR;
+  }
+  a.d_angles = u.angles.ptr;
+  a.d_x = u.x.ptr;
+  a.d_offsets = u.d_offsets();
+  a.d_p = d_p.ptr;
+  a.d_covar = d_covar.ptr;
+  a.d_stats = d_stats.ptr;
+  a.d_rank = reinterpret_cast<int *>(d_rank.ptr);
+  if (packed_stats_run(a, who) != 0) return LM_ERROR;
+  e = hipStreamSynchronize(nullptr);
+  if (e == hipSuccess && covar) e = hipMemcpy(covar, d_covar.ptr, sizeof(double) * 9 * S, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && stats) e = hipMemcpy(stats, d_stats.ptr, sizeof(double) * BRDF_STATS_SZ * S, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && rank) e = hipMemcpy(rank, d_rank.ptr, sizeof(int) * S, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    set_error("%s(): %s", who, hipGetErrorString(e));
+    return LM_ERROR;
+  }
+  return 0;
+}
+
+int brdf_hip_last_packed_stats(int cls, long long *fits, int *stride, int *chunks) {
+  if (cls < 0 || cls >= kPackedClasses) return LM_ERROR;
+  const PackedLastStats st = packed_last_stats();
+  if (fits) *fits = st.fits[cls];
+  if (stride) *stride = st.stride[cls];
+  if (chunks) *chunks = st.chunks[cls];
+  return 0;
 }
 
 int brdf_hip_model_eval_dev(int model, const double *d_angles, int n, const double *p, double *d_hx, void *stream) {

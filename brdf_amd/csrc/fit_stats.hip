@@ -32,6 +32,7 @@
 #include "../../include/brdf_levmar.h"
 #include "fit_stats.h"
 #include "fit_host.h"
+#include "packed_plan.h"
 
 namespace brdf {
 
@@ -42,6 +43,10 @@ constexpr int kRow = kNS + 1;  // + sum (x - mean)^2
 constexpr int kRowsThreads = 512, kRowsFits = kRowsThreads / 16;
 constexpr int kWaveThreads = 256, kWaveFits = kWaveThreads / kWave, kWaveMaxN = 256, kWavePer = kWaveMaxN / kWave;
 constexpr int kBlockThreads = 256, kBlockMaxN = 4096;
+// (a packed batch's size classes, packed_plan.h, step wherever these kernels change: rows | wave | workgroup | chunked)
+static_assert(packed_class(16) + 1 == packed_class(17) && packed_class(kWaveMaxN) + 1 == packed_class(kWaveMaxN + 1) &&
+                  packed_class(kBlockMaxN) + 1 == packed_class(kBlockMaxN + 1) && packed_class(kBlockMaxN + 1) == kPackedLargeClass,
+              "packed_plan.h: the statistics kernels' bounds are size-class bounds");
 constexpr int kMaxPartials = kBlockThreads;  // workgroups per fit at most (n > 4096): the folds hold one partial row per thread
 
 constexpr int kMaxSamples = 0x7fffffff - 2 * kMaxPartials * kBlockThreads;  // largest n: no index of a sweep overflows

@@ -254,6 +254,94 @@ def fit_stats_batch(method: int, model: int, angles, x, p, *, opts=None, counts=
     return FitStats(covar, stats, rank)
 
 
+def pack_samples(angles, x, counts):
+    """Padded rows -> a packed batch: angles [S,3,n], x [S,n], counts [S] (integers; torch tensors on one device, or numpy arrays)
+    -> (angles [3 * total] float64, x [total], offsets [S+1] int64) of the same kind, total = sum(counts).  Fit s's first counts[s]
+    samples are laid back to back: its three planes at angles[3 * offsets[s]:], counts[s] values each, its measurements at
+    x[offsets[s]:] -- the layout fit_batch_packed reads, and the inverse of what its gather does.  Entries at and behind a count
+    (NaN padding included) do not travel; a count outside [0, n] is clipped.  compact_samples -> pack_samples -> fit_batch_packed is
+    a pipeline."""
+    if isinstance(x, np.ndarray):
+        _require(x.ndim == 2 and angles.shape == (x.shape[0], 3, x.shape[1]) and np.shape(counts) == (x.shape[0],), "angles [S,3,n], x [S,n], counts [S]")
+        k = np.clip(np.asarray(counts).astype(np.int64), 0, x.shape[1])
+        keep = np.arange(x.shape[1])[None, :] < k[:, None]
+        offsets = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(k)])
+        return (np.ascontiguousarray(angles[np.broadcast_to(keep[:, None, :], angles.shape)], dtype=np.float64),
+                np.ascontiguousarray(x[keep], dtype=np.float64), offsets)
+    import torch
+    _require(x.dim() == 2 and tuple(angles.shape) == (x.shape[0], 3, x.shape[1]) and tuple(counts.shape) == (x.shape[0],), "angles [S,3,n], x [S,n], counts [S]")
+    k = counts.to(torch.int64).clamp(0, x.shape[1])
+    keep = torch.arange(x.shape[1], device=x.device)[None, :] < k[:, None]
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=x.device), torch.cumsum(k, 0)])
+    return angles[keep[:, None, :].expand(angles.shape)].to(torch.float64), x[keep].to(torch.float64), offsets
+
+
+def _packed_args(angles, x, offsets, p, validate, torch):
+    _require(angles.is_cuda and x.is_cuda and offsets.is_cuda and p.is_cuda and angles.device == x.device == offsets.device == p.device,
+             "angles, x, offsets, p: CUDA tensors on one device")
+    _require(angles.dtype == torch.float64 and x.dtype == torch.float64 and p.dtype == torch.float64 and offsets.dtype == torch.int64,
+             "angles, x, p: float64; offsets: int64")  # the kernels read raw doubles and long longs
+    _require(offsets.dim() == 1 and offsets.numel() >= 2 and p.dim() == 2 and tuple(p.shape) == (offsets.numel() - 1, 3),
+             "offsets [S+1], p [S,3]")
+    _require(angles.dim() == 1 and x.dim() == 1 and angles.numel() >= 3 * x.numel(), "angles [3 * total], x [total]: flat, packed")
+    if validate:  # (synchronises: the packed calls wait for the stream anyway)
+        lo, hi = int(offsets[0]), int(offsets[-1])
+        _require(0 <= lo <= hi <= x.numel(), f"offsets cover [{lo}, {hi}), x holds {x.numel()} samples")
+        _require(bool((offsets[1:] >= offsets[:-1]).all()), "offsets must not decrease")
+    return angles.contiguous(), x.contiguous(), offsets.contiguous(), p.contiguous()
+
+
+def fit_batch_packed(method: int, model: int, angles, x, offsets, p0, *, lb=None, ub=None, itmax=100, opts=None, workspace_bytes: int = 0,
+                     validate: bool = True):
+    """S fits of ANY size in one call (brdf_hip_fit_batch_packed_dev): a packed batch, bucketed by size class inside the library.
+    angles: CUDA float64 [3 * total], x: [total], offsets: CUDA int64 [S+1] (pack_samples builds all three), p0: CUDA float64 [S,3]
+    (updated in place).  Fit s has k = offsets[s+1] - offsets[s] samples: planes [3][k] at angles[3 * offsets[s]:], measurements at
+    x[offsets[s]:].  A fit of k >= 3 samples gets the bytes fit_batch gives it alone at n = k; k < 3: ret -1, zero info, p as it came.
+    workspace_bytes bounds the padded rows of one chunk (0: 1 GiB).  validate=False skips the range check of the offsets (callers that
+    vouch for them).  Returns (p [S,3], info [S,10], ret [S] int32) as CUDA tensors; the call waits for the stream once."""
+    import torch
+    angles, x, offsets, p = _packed_args(angles, x, offsets, p0, validate, torch)
+    S = offsets.numel() - 1
+    info = torch.zeros((S, 10), dtype=torch.float64, device=x.device)
+    ret = torch.zeros((S,), dtype=torch.int32, device=x.device)
+    lb_a, ub_a, op_a = _f64(lb, 3), _f64(ub, 3), _f64(opts, 5)
+    with torch.cuda.device(x.device):
+        rc = lib.brdf_hip_fit_batch_packed_dev(method, model, angles.data_ptr(), x.data_ptr(), offsets.data_ptr(), S, p.data_ptr(), _dptr(lb_a),
+                                               _dptr(ub_a), itmax, _dptr(op_a), info.data_ptr(), ret.data_ptr(), int(workspace_bytes),
+                                               _stream_handle(torch))
+    if rc != 0:
+        raise RuntimeError(f"brdf_hip_fit_batch_packed_dev failed: {last_error()}")
+    return p, info, ret
+
+
+def fit_stats_batch_packed(method: int, model: int, angles, x, offsets, p, *, opts=None, workspace_bytes: int = 0, validate: bool = True) -> FitStats:
+    """fit_stats_batch for a packed batch (brdf_hip_fit_stats_batch_packed_dev): arguments as fit_batch_packed, p [S,3] read only.
+    Every fit's covar / stats / rank are the bytes fit_stats_batch gives it alone at n = its count; a count below 3: rank 0."""
+    import torch
+    angles, x, offsets, p = _packed_args(angles, x, offsets, p, validate, torch)
+    S = offsets.numel() - 1
+    covar = torch.zeros((S, 3, 3), dtype=torch.float64, device=x.device)
+    stats = torch.zeros((S, 8), dtype=torch.float64, device=x.device)
+    rank = torch.zeros((S,), dtype=torch.int32, device=x.device)
+    op_a = _f64(opts, 5)
+    with torch.cuda.device(x.device):
+        rc = lib.brdf_hip_fit_stats_batch_packed_dev(method, model, angles.data_ptr(), x.data_ptr(), offsets.data_ptr(), S, p.data_ptr(), _dptr(op_a),
+                                                     covar.data_ptr(), stats.data_ptr(), rank.data_ptr(), int(workspace_bytes), _stream_handle(torch))
+    if rc != 0:
+        raise RuntimeError(f"brdf_hip_fit_stats_batch_packed_dev failed: {last_error()}")
+    return FitStats(covar, stats, rank)
+
+
+def last_packed_stats() -> list:
+    """per size class 0..5 (<= 16, 64, 256, 1024, 4096 samples, above) of this thread's last packed call: fits, the row stride of its
+    launches (0: empty class; class 5: the largest count) and chunks (class 5: one run per fit)"""
+    out = []
+    fits, stride, chunks = C.c_longlong(0), C.c_int(0), C.c_int(0)
+    while lib.brdf_hip_last_packed_stats(len(out), C.byref(fits), C.byref(stride), C.byref(chunks)) == 0:
+        out.append({"fits": fits.value, "stride": stride.value, "chunks": chunks.value})
+    return out
+
+
 def fit_batch_multi(method: int, model: int, angles, x, p0, *, devices=None, lb=None, ub=None, itmax=100, opts=None):
     """S independent fits over several GPUs of this process (brdf_hip_fit_batch_multi): HOST arrays angles [S,3,n], x [S,n],
     p0 [S,3] (not modified).  `devices`: HIP ordinals, one contiguous shard of ceil(S/len) fits each (dist.shard_range; an

@@ -267,7 +267,7 @@ int brdf_hip_fit_stats_batch(int method, int model, const double *angles, const 
  *               there are (both 0 for a count of 0 or out of range).
  *   Kernel      chosen by the stride n, as in the uniform calls: a batch whose counts span several size classes (<= 16, 64, 256,
  *               1024, 4096) runs EVERY fit in the stride's class -- a fit of 5 samples in rows of 4096 occupies a whole workgroup.
- *               Callers with very unequal counts should bucket their fits by size class and make one call per class.  Within the
+ *               Batches with very unequal counts belong in the packed entries below, which bucket by size class.  Within the
  *               stride's own class a fit's p / info / ret (and covar / stats / rank) are bit-identical to the uniform call with
  *               n = counts[s] on that fit alone; below it they agree as two summation orders do.
  *   n > 4096    the fits run one after the other through the single-fit regimes with n = counts[s] (the counts are copied to the
@@ -286,6 +286,49 @@ int brdf_hip_fit_stats_batch_ragged_dev(int method, int model, const double *d_a
                                         void *stream);
 int brdf_hip_fit_stats_batch_ragged(int method, int model, const double *angles, const double *x, const int *counts, int S, int n,
                                     const double *p, const double *opts, double *covar, double *stats, int *rank);
+
+/* ---- packed batches: fits of any size in one call (extensions) --------------------------------------------- */
+/* S fits laid back to back, CSR style, bucketed by size class (<= 16, 64, 256, 1024, 4096 samples, and above) inside the library:
+ * what a caller of the ragged entries above had to do by hand when the counts of a batch span several classes.
+ *   Layout      d_offsets[S + 1]: a DEVICE array of long long (HOST in the two host-pointer entries), non-decreasing; fit s has
+ *               k_s = offsets[s + 1] - offsets[s] samples.  Its three planes are k_s doubles each, contiguous, at d_angles + 3 * offsets[s]
+ *               -- the single-fit layout of brdf_hip_fit_dev -- and its measurements at d_x + offsets[s].  offsets[0] need not be 0;
+ *               nothing outside [offsets[0], offsets[S]) is ever read.  The uniform batch angles[S][3][n] is offsets[s] = s * n.
+ *               d_p[S][3], d_info[S][10] (or NULL), d_ret[S] (or NULL) are the uniform call's.
+ *   Definition  for k_s >= 3, fit s returns the BYTES brdf_hip_fit_batch_dev returns for that fit alone with n = k_s (covar / stats /
+ *               rank: those of brdf_hip_fit_stats_batch_dev), whatever else is in the batch and wherever the fit stands in it.
+ *   Too few     0 <= k_s < 3 is levmar's n < m refusal, as in the ragged call: ret[s] = LM_ERROR, info[s] all zeros, p[s] as it came;
+ *               the statistics are what the ragged pass writes for such a count (rank 0, zeros; sumsq and R2 over the samples there are).
+ *   Decreasing  a negative difference of two offsets (and, in the device entries, one above INT_MAX) is treated as a count of 0.
+ *   How         a plan on the device (count and class of every fit; a stable partition of the fit indices by class), then per class,
+ *               in chunks of what the workspace holds: a gather of the chunk's segments into padded rows of the class's largest
+ *               count, the ragged call of that class, a scatter of the results to the caller's rows.  Fits above 4096 samples are
+ *               not copied: they run where they lie, one after the other, each spread over the chip, as in the uniform call.
+ *   One wait    the call waits for `stream` ONCE, to read the plan (six fit counts, six largest counts) back.  With fits above 4096
+ *               samples it waits again around them, as the uniform call does (their starting points travel to the host in one copy,
+ *               their results back in one).  The rest is asynchronous on `stream`.
+ *   Workspace   stream-ordered allocations (hipMallocAsync / hipFreeAsync) bounded by workspace_bytes; 0: 1 GiB.  A chunk holds
+ *               max(1, workspace_bytes / bytes per padded fit) fits, bytes per padded fit = 8 * (4 * stride + 30) + 12, stride = the
+ *               class's largest count (at least 3).  The size of a chunk never shows in a result.
+ *   Checks      null pointers, S <= 0, workspace_bytes < 0, an unknown model / method, lb > ub -- and in the host-pointer entries
+ *               offsets that decrease and a fit of more than INT_MAX samples -- are refused before any HIP call.
+ *   Host entries  upload the offsets[S] - offsets[0] samples the batch covers; brdf_hip_fit_batch_packed returns the number of fits
+ *               that ended in LM_ERROR (refused ones included), as brdf_hip_fit_batch does.
+ * Not covered: per-sample weights, dscl, a packed brdf_hip_fit_batch_multi, a capture entry that groups faces. */
+int brdf_hip_fit_batch_packed_dev(int method, int model, const double *d_angles, const double *d_x, const long long *d_offsets, int S,
+                                  double *d_p, const double *lb, const double *ub, int itmax, const double *opts, double *d_info, int *d_ret,
+                                  long long workspace_bytes, void *stream);
+int brdf_hip_fit_batch_packed(int method, int model, const double *angles, const double *x, const long long *offsets, int S, double *p,
+                              const double *lb, const double *ub, int itmax, const double *opts, double *info, int *ret,
+                              long long workspace_bytes);
+int brdf_hip_fit_stats_batch_packed_dev(int method, int model, const double *d_angles, const double *d_x, const long long *d_offsets, int S,
+                                        const double *d_p, const double *opts, double *d_covar, double *d_stats, int *d_rank,
+                                        long long workspace_bytes, void *stream);
+int brdf_hip_fit_stats_batch_packed(int method, int model, const double *angles, const double *x, const long long *offsets, int S,
+                                    const double *p, const double *opts, double *covar, double *stats, int *rank, long long workspace_bytes);
+/* class cls (0: <= 16 samples ... 4: <= 4096, 5: above) of the calling thread's last packed call: its fits, the row stride of its
+ * launches (0 for an empty class; class 5: the largest count) and its chunks (class 5: one run per fit).  LM_ERROR for another cls. */
+int brdf_hip_last_packed_stats(int cls, long long *fits, int *stride, int *chunks);
 
 /* hx[i] = model(p; sample i) for device-resident planes; d_hx DEVICE pointer, p HOST pointer. */
 int brdf_hip_model_eval_dev(int model, const double *d_angles, int n, const double *p, double *d_hx,
