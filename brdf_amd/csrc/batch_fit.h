@@ -24,7 +24,21 @@ struct BatchFitArgs {
   // ragged batch (device, [S], or null): fit s uses samples [0, d_counts[s]) of its rows; n stays the row stride
   const int *d_counts = nullptr;
 };
-int batch_fit_enqueue(const BatchFitArgs &a);
+// argument check (no HIP call) and enqueue; `who` names the entry point in error texts.  Asynchronous on a.stream up to 4096 samples per fit.
+int batch_fit_check(const BatchFitArgs &a, const char *who);
+int batch_fit_enqueue(const BatchFitArgs &a, const char *who);
+
+// A fit above 4096 samples no longer fits a workgroup: the batched entries run such fits one after the other through the single-fit
+// path, each spread over the chip.
+struct BigFit {
+  const double *d_angles, *d_x;  // three planes `stride` apart, the measurements
+  int k, stride;                 // the fit's own sample count; k == stride: the planes already lie as a single fit reads them
+  long long row;                 // the fit's row of the caller's arrays
+};
+// fits[0, count) from host p[rows][3] into host p, info[rows][10] and ret[rows]; method, model, box, itmax, opts and stream are a's.  A
+// count below 3 or above the stride is levmar's n < m refusal (lm_core.c:502, lmbc_core.c:440) without a launch: ret -1, info and p as
+// they are.  The caller waits for a.stream before the host arrays go away.
+int big_fits_run(const BatchFitArgs &a, const BigFit *fits, int count, double *p, double *info, int *ret);
 
 constexpr int kNeedsExact = -2;  // flag value: this fit has a cosine <= 0 and must take the exact model path
 

@@ -737,39 +737,39 @@ int batch_fit_launches(const BatchFitArgs &a, MethodSpec ms, const Geometry &g, 
 
 // n > 4096 samples per fit: a fit no longer fits one workgroup's registers + LDS, but it fits the CHIP -- the fits run one
 // after the other through the single-fit path (resident regime up to #CUs * 4096 samples, the launch chain beyond), each
-// using every CU.  The starting points travel to the host and the results back: synchronous on a.stream.
+// using every CU.
+int big_fits_run(const BatchFitArgs &a, const BigFit *fits, int count, double *p, double *info, int *ret) {
+  MethodSpec ms;
+  (void)method_spec(a.method, &ms);
+  DeviceBlock<double> pack;
+  for (int j = 0; j < count; ++j) {
+    const BigFit &f = fits[j];
+    if (f.k < kM || f.k > f.stride) {
+      ret[f.row] = kLmError;
+      continue;
+    }
+    if (f.k != f.stride && pack_plane_prefixes(f, pack, a.stream) != 0) return kLmError;
+    ret[f.row] = stream_fit_run(stream_fit_args(ms, a.model, f.k != f.stride ? pack.ptr : f.d_angles, f.d_x, f.k, p + f.row * kM, a.lb, a.ub, nullptr,
+                                                a.itmax, a.opts, info + f.row * kInfoSz, nullptr, a.stream));
+  }
+  return 0;
+}
+
+// The uniform and the ragged batch above 4096 samples.  The starting points (and the counts) travel to the host and the results
+// back: synchronous on a.stream.
 namespace {
-int batch_of_large_fits(const BatchFitArgs &a, MethodSpec ms) {
+int batch_of_big_fits(const BatchFitArgs &a) {
   std::vector<double> p((size_t)a.S * kM), info((size_t)a.S * kInfoSz);
-  std::vector<int> ret(a.S);
-  std::vector<int> counts;  // ragged: the counts travel to the host next to p
+  std::vector<int> ret(a.S), counts;
   HIP_OK(hipMemcpyAsync(p.data(), a.d_p, sizeof(double) * p.size(), hipMemcpyDeviceToHost, a.stream));
   if (a.d_counts) {
     counts.resize(a.S);
     HIP_OK(hipMemcpyAsync(counts.data(), a.d_counts, sizeof(int) * counts.size(), hipMemcpyDeviceToHost, a.stream));
   }
   HIP_OK(hipStreamSynchronize(a.stream));
-  DeviceBlock<double> pack;  // a ragged fit's three plane prefixes, next to each other as a single fit reads them
-  for (int s = 0; s < a.S; ++s) {
-    const double *angles = a.d_angles + (size_t)s * 3 * a.n;
-    int k = a.n;
-    if (a.d_counts) {
-      k = counts[s];
-      if (k < kM || k > a.n) {  // levmar's n < m refusal (lm_core.c:502, lmbc_core.c:440), without a launch: info stays zero, p as it came
-        ret[s] = kLmError;
-        continue;
-      }
-      if (k != a.n) {
-        HIP_OK(pack.ensure(3 * (size_t)a.n));
-        for (int pl = 0; pl < 3; ++pl)
-          HIP_OK(hipMemcpyAsync(pack.ptr + (size_t)pl * k, angles + (size_t)pl * a.n, sizeof(double) * k, hipMemcpyDeviceToDevice, a.stream));
-        angles = pack.ptr;
-      }
-    }
-    const StreamFitArgs f = stream_fit_args(ms, a.model, angles, a.d_x + (size_t)s * a.n, k, p.data() + (size_t)s * kM,
-                                            a.lb, a.ub, nullptr, a.itmax, a.opts, info.data() + (size_t)s * kInfoSz, nullptr, a.stream);
-    ret[s] = stream_fit_run(f);
-  }
+  std::vector<BigFit> fits(a.S);
+  for (int s = 0; s < a.S; ++s) fits[s] = {a.d_angles + (size_t)s * 3 * a.n, a.d_x + (size_t)s * a.n, a.d_counts ? counts[s] : a.n, a.n, s};
+  if (big_fits_run(a, fits.data(), a.S, p.data(), info.data(), ret.data()) != 0) return kLmError;
   HIP_OK(hipMemcpyAsync(a.d_p, p.data(), sizeof(double) * p.size(), hipMemcpyHostToDevice, a.stream));
   if (a.d_info) HIP_OK(hipMemcpyAsync(a.d_info, info.data(), sizeof(double) * info.size(), hipMemcpyHostToDevice, a.stream));
   if (a.d_ret) HIP_OK(hipMemcpyAsync(a.d_ret, ret.data(), sizeof(int) * ret.size(), hipMemcpyHostToDevice, a.stream));
@@ -778,24 +778,24 @@ int batch_of_large_fits(const BatchFitArgs &a, MethodSpec ms) {
 }
 }  // namespace
 
-int batch_fit_enqueue(const BatchFitArgs &a) {
+int batch_fit_check(const BatchFitArgs &a, const char *who) {
   MethodSpec ms;
-  if (a.model < 0 || a.model >= MODEL_COUNT || !method_spec(a.method, &ms)) {
-    set_error("brdf_hip_fit_batch_dev(): unknown model %d / method %d", a.model, a.method);
-    return kLmError;
-  }
+  if (!known_model_method(a.model, a.method, &ms, who)) return kLmError;
   if (!a.d_angles || !a.d_x || !a.d_p || a.S <= 0 || a.n <= 0) {
-    set_error("brdf_hip_fit_batch_dev(): null device pointer or non-positive S/n");
+    set_error("%s(): null pointer or non-positive S/n", who);
     return kLmError;
   }
   Geometry g;
-  if (!geometry_for(a.n, &g)) return batch_of_large_fits(a, ms);  // n > 4096: one fit after the other, each spread over the chip
-  if (ms.machine == kBcMachine && a.lb && a.ub)
-    for (int i = 0; i < kM; ++i)
-      if (a.lb[i] > a.ub[i]) {  // lmbc_core.c:451-454
-        set_bad_input_error("dlevmar_bc_dif", 2, a.n, kM);
-        return kLmError;
-      }
+  if (!geometry_for(a.n, &g)) return 0;  // (fits above 4096 samples leave before the box is looked at: the single-fit path refuses each, ret -1)
+  return box_refused(ms, a.lb, a.ub, who) ? kLmError : 0;
+}
+
+int batch_fit_enqueue(const BatchFitArgs &a, const char *who) {
+  if (batch_fit_check(a, who) != 0) return kLmError;
+  MethodSpec ms;
+  (void)method_spec(a.method, &ms);
+  Geometry g;
+  if (!geometry_for(a.n, &g)) return batch_of_big_fits(a);  // n > 4096: one fit after the other, each spread over the chip
   (void)hipGetLastError();
   int dev = 0;
   HIP_OK(hipGetDevice(&dev));

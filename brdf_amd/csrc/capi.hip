@@ -76,15 +76,6 @@ hipError_t upload_planes(double *d, const double *angles, int n, int model) {
   return e;
 }
 
-// scoped device buffer
-using DevBuf = DeviceBlock<double>;
-int alloc_doubles(DevBuf &b, size_t count) {
-  const hipError_t e = b.ensure(count);
-  if (e == hipSuccess) return 0;
-  set_error("hipMalloc(%zu doubles) failed: %s", count, hipGetErrorString(e));
-  return -1;
-}
-
 int host_fit(MethodSpec ms, const char *who, model_func_t func, double *p, double *x, int m, int n, double *lb,
              double *ub, double *dscl, int itmax, double *opts, double *info, double *covar, void *adata) {
   if (!func) {
@@ -474,91 +465,61 @@ int brdf_hip_last_channels_stats(int channel, int *shared_launch, long long *pas
 int brdf_hip_fit_batch_dev(int method, int model, const double *d_angles, const double *d_x, int S, int n,
                            double *d_p, const double *lb, const double *ub, int itmax, const double *opts,
                            double *d_info, int *d_ret, void *stream) {
-  BatchFitArgs a;
-  a.method = method;
-  a.model = model;
-  a.d_angles = d_angles;
-  a.d_x = d_x;
-  a.S = S;
-  a.n = n;
-  a.d_p = d_p;
-  a.lb = lb;
-  a.ub = ub;
-  a.itmax = itmax;
-  a.opts = opts;
-  a.d_info = d_info;
-  a.d_ret = d_ret;
-  a.stream = static_cast<hipStream_t>(stream);
-  return batch_fit_enqueue(a);
+  const BatchFitArgs a = {method, model, d_angles, d_x, S, n, d_p, lb, ub, itmax, opts, d_info, d_ret, static_cast<hipStream_t>(stream)};
+  return batch_fit_enqueue(a, "brdf_hip_fit_batch_dev");
 }
 
 int brdf_hip_fit_batch_ragged_dev(int method, int model, const double *d_angles, const double *d_x, const int *d_counts, int S, int n,
                                   double *d_p, const double *lb, const double *ub, int itmax, const double *opts, double *d_info,
                                   int *d_ret, void *stream) {
-  BatchFitArgs a;
-  a.method = method;
-  a.model = model;
-  a.d_angles = d_angles;
-  a.d_x = d_x;
-  a.d_counts = d_counts;  // (null: the uniform call)
-  a.S = S;
-  a.n = n;
-  a.d_p = d_p;
-  a.lb = lb;
-  a.ub = ub;
-  a.itmax = itmax;
-  a.opts = opts;
-  a.d_info = d_info;
-  a.d_ret = d_ret;
-  a.stream = static_cast<hipStream_t>(stream);
-  return batch_fit_enqueue(a);
+  const BatchFitArgs a = {method, model, d_angles, d_x, S, n, d_p, lb, ub, itmax, opts, d_info, d_ret, static_cast<hipStream_t>(stream),
+                          d_counts};  // (null: the uniform call)
+  return batch_fit_enqueue(a, "brdf_hip_fit_batch_ragged_dev");
 }
 
 namespace {
+// The host-pointer twins: the entry's own argument check on the host pointers (no HIP call before it), a HostCall (fit_host.h) for the
+// device copies, the _dev twin's enqueue, one wait.  The fits return the number of fits with ret < 0.
+int count_failed(const int *ret, int S) {
+  int bad = 0;
+  for (int s = 0; s < S; ++s) bad += ret[s] < 0;
+  return bad;
+}
+
 // brdf_hip_fit_batch and its ragged twin (counts: host, or null)
 int fit_batch_host(const char *who, int method, int model, const double *angles, const double *x, const int *counts, int S, int n, double *p,
                    const double *lb, const double *ub, int itmax, const double *opts, double *info, int *ret) {
-  if (!angles || !x || !p || S <= 0 || n <= 0) {
-    set_error("%s(): bad arguments", who);
-    return LM_ERROR;
-  }
-  if (counts && (model < 0 || model >= brdf::MODEL_COUNT || method < BRDF_METHOD_DIF || method > BRDF_METHOD_DER)) {  // before any HIP call
-    set_error("%s(): unknown model %d / method %d", who, model, method);
-    return LM_ERROR;
-  }
+  BatchFitArgs a = {method, model, angles, x, S, n, p, lb, ub, itmax, opts, info, ret, nullptr, counts};
+  if (batch_fit_check(a, who) != 0) return LM_ERROR;
+  std::vector<int> own_ret(ret ? 0 : S);
+  if (!ret) ret = own_ret.data();
   const size_t sn = (size_t)S * n;
-  DevBuf d_angles, d_x, d_p, d_info, d_ret, d_counts;
-  if (alloc_doubles(d_angles, 3 * sn) || alloc_doubles(d_x, sn) || alloc_doubles(d_p, 3 * (size_t)S) || alloc_doubles(d_info, 10 * (size_t)S) ||
-      alloc_doubles(d_ret, ((size_t)S + 1) / 2 + 1) || (counts && alloc_doubles(d_counts, ((size_t)S + 1) / 2 + 1)))
-    return LM_ERROR;
-  hipError_t e = hipMemcpy(d_angles.ptr, angles, sizeof(double) * 3 * sn, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_x.ptr, x, sizeof(double) * sn, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_p.ptr, p, sizeof(double) * 3 * S, hipMemcpyHostToDevice);
-  if (e == hipSuccess && counts) e = hipMemcpy(d_counts.ptr, counts, sizeof(int) * S, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    set_error("%s(): host->device copy failed: %s", who, hipGetErrorString(e));
-    return LM_ERROR;
-  }
-  int *d_ret_i = reinterpret_cast<int *>(d_ret.ptr);
-  if (brdf_hip_fit_batch_ragged_dev(method, model, d_angles.ptr, d_x.ptr, counts ? reinterpret_cast<const int *>(d_counts.ptr) : nullptr, S, n,
-                                    d_p.ptr, lb, ub, itmax, opts, d_info.ptr, d_ret_i, nullptr) != 0)
-    return LM_ERROR;
-  e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(p, d_p.ptr, sizeof(double) * 3 * S, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && info) e = hipMemcpy(info, d_info.ptr, sizeof(double) * 10 * S, hipMemcpyDeviceToHost);
-  int *host_ret = ret;
-  int *tmp = nullptr;
-  if (!host_ret) host_ret = tmp = new int[S];
-  if (e == hipSuccess) e = hipMemcpy(host_ret, d_ret_i, sizeof(int) * S, hipMemcpyDeviceToHost);
-  int bad = 0;
-  if (e == hipSuccess)
-    for (int s = 0; s < S; ++s) bad += host_ret[s] < 0;
-  delete[] tmp;
-  if (e != hipSuccess) {
-    set_error("%s(): %s", who, hipGetErrorString(e));
-    return LM_ERROR;
-  }
-  return bad;
+  HostCall h(who);
+  a.d_angles = h.in(angles, 3 * sn);
+  a.d_x = h.in(x, sn);
+  a.d_counts = h.in(counts, S);
+  a.d_p = h.inout(p, 3 * (size_t)S);
+  a.d_info = h.out(info, 10 * (size_t)S);
+  a.d_ret = h.out(ret, S);
+  if (h.failed() || batch_fit_enqueue(a, who) != 0 || h.finish() != 0) return LM_ERROR;
+  return count_failed(ret, S);
+}
+
+int fit_stats_host(const char *who, int method, int model, const double *angles, const double *x, const int *counts, int S, int n,
+                   const double *p, const double *opts, double *covar, double *stats, int *rank) {
+  FitStatsArgs a = {method, model, angles, x, S, n, p, opts, covar, stats, rank, nullptr, 0, nullptr, counts};
+  if (fit_stats_check(a, who) != 0) return LM_ERROR;
+  const size_t sn = (size_t)S * n;
+  HostCall h(who);
+  a.d_angles = h.in(angles, 3 * sn);
+  a.d_x = h.in(x, sn);
+  a.d_counts = h.in(counts, S);
+  a.d_p = h.in(p, 3 * (size_t)S);
+  a.d_covar = h.out(covar, 9 * (size_t)S);
+  a.d_stats = h.out(stats, BRDF_STATS_SZ * (size_t)S);
+  a.d_rank = h.out(rank, S);
+  if (h.failed() || fit_stats_enqueue(a, who) != 0 || h.finish() != 0) return LM_ERROR;
+  return 0;
 }
 }  // namespace
 
@@ -575,91 +536,17 @@ int brdf_hip_fit_batch_ragged(int method, int model, const double *angles, const
 int brdf_hip_fit_stats_batch_dev(int method, int model, const double *d_angles, const double *d_x, int S, int n,
                                  const double *d_p, const double *opts, double *d_covar, double *d_stats, int *d_rank,
                                  void *stream) {
-  FitStatsArgs a;
-  a.method = method;
-  a.model = model;
-  a.d_angles = d_angles;
-  a.d_x = d_x;
-  a.S = S;
-  a.n = n;
-  a.d_p = d_p;
-  a.opts = opts;
-  a.d_covar = d_covar;
-  a.d_stats = d_stats;
-  a.d_rank = d_rank;
-  a.stream = static_cast<hipStream_t>(stream);
+  const FitStatsArgs a = {method, model, d_angles, d_x, S, n, d_p, opts, d_covar, d_stats, d_rank, nullptr, 0, static_cast<hipStream_t>(stream)};
   return fit_stats_enqueue(a, "brdf_hip_fit_stats_batch_dev");
 }
 
 int brdf_hip_fit_stats_batch_ragged_dev(int method, int model, const double *d_angles, const double *d_x, const int *d_counts, int S,
                                         int n, const double *d_p, const double *opts, double *d_covar, double *d_stats, int *d_rank,
                                         void *stream) {
-  FitStatsArgs a;
-  a.method = method;
-  a.model = model;
-  a.d_angles = d_angles;
-  a.d_x = d_x;
-  a.d_counts = d_counts;  // (null: the uniform call)
-  a.S = S;
-  a.n = n;
-  a.d_p = d_p;
-  a.opts = opts;
-  a.d_covar = d_covar;
-  a.d_stats = d_stats;
-  a.d_rank = d_rank;
-  a.stream = static_cast<hipStream_t>(stream);
+  const FitStatsArgs a = {method, model, d_angles, d_x, S, n, d_p, opts, d_covar, d_stats, d_rank, nullptr, 0, static_cast<hipStream_t>(stream),
+                          d_counts};  // (null: the uniform call)
   return fit_stats_enqueue(a, "brdf_hip_fit_stats_batch_ragged_dev");
 }
-
-namespace {
-int fit_stats_host(const char *who, int method, int model, const double *angles, const double *x, const int *counts, int S, int n,
-                   const double *p, const double *opts, double *covar, double *stats, int *rank) {
-  FitStatsArgs a;
-  a.method = method;
-  a.model = model;
-  a.d_angles = angles;  // (host pointers: checked for null only)
-  a.d_x = x;
-  a.S = S;
-  a.n = n;
-  a.d_p = p;
-  a.opts = opts;
-  a.d_covar = covar;
-  a.d_stats = stats;
-  a.d_rank = rank;
-  if (fit_stats_check(a, who) != 0) return LM_ERROR;
-  const size_t sn = (size_t)S * n;
-  DevBuf d_angles, d_x, d_p, d_covar, d_stats, d_rank, d_counts;
-  if (alloc_doubles(d_angles, 3 * sn) || alloc_doubles(d_x, sn) || alloc_doubles(d_p, 3 * (size_t)S) || (covar && alloc_doubles(d_covar, 9 * (size_t)S)) ||
-      (stats && alloc_doubles(d_stats, BRDF_STATS_SZ * (size_t)S)) || (rank && alloc_doubles(d_rank, ((size_t)S + 1) / 2 + 1)) ||
-      (counts && alloc_doubles(d_counts, ((size_t)S + 1) / 2 + 1)))
-    return LM_ERROR;
-  hipError_t e = hipMemcpy(d_angles.ptr, angles, sizeof(double) * 3 * sn, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_x.ptr, x, sizeof(double) * sn, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_p.ptr, p, sizeof(double) * 3 * S, hipMemcpyHostToDevice);
-  if (e == hipSuccess && counts) e = hipMemcpy(d_counts.ptr, counts, sizeof(int) * S, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    set_error("%s(): host->device copy failed: %s", who, hipGetErrorString(e));
-    return LM_ERROR;
-  }
-  a.d_counts = counts ? reinterpret_cast<const int *>(d_counts.ptr) : nullptr;
-  a.d_angles = d_angles.ptr;
-  a.d_x = d_x.ptr;
-  a.d_p = d_p.ptr;
-  a.d_covar = d_covar.ptr;
-  a.d_stats = d_stats.ptr;
-  a.d_rank = reinterpret_cast<int *>(d_rank.ptr);
-  if (fit_stats_enqueue(a, who) != 0) return LM_ERROR;
-  e = hipStreamSynchronize(nullptr);
-  if (e == hipSuccess && covar) e = hipMemcpy(covar, d_covar.ptr, sizeof(double) * 9 * S, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && stats) e = hipMemcpy(stats, d_stats.ptr, sizeof(double) * BRDF_STATS_SZ * S, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && rank) e = hipMemcpy(rank, d_rank.ptr, sizeof(int) * S, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) {
-    set_error("%s(): %s", who, hipGetErrorString(e));
-    return LM_ERROR;
-  }
-  return 0;
-}
-}  // namespace
 
 int brdf_hip_fit_stats_batch(int method, int model, const double *angles, const double *x, int S, int n, const double *p,
                              const double *opts, double *covar, double *stats, int *rank) {
@@ -705,65 +592,32 @@ int check_host_offsets(const char *who, const long long *offsets, int S) {
 }
 
 // the samples [offsets[0], offsets[S]) and the offsets, rebased to 0, on the device
-struct PackedUpload {
-  DevBuf angles, x, offsets;
-  const long long *d_offsets() const { return reinterpret_cast<const long long *>(offsets.ptr); }
-};
-int upload_packed(const char *who, const double *angles, const double *x, const long long *offsets, int S, PackedUpload *u) {
+void upload_packed(HostCall &h, const double *angles, const double *x, const long long *offsets, int S, const double **d_angles, const double **d_x,
+                   const long long **d_offsets) {
   const size_t total = (size_t)(offsets[S] - offsets[0]);
-  if (alloc_doubles(u->angles, 3 * total + 1) || alloc_doubles(u->x, total + 1) || alloc_doubles(u->offsets, (size_t)S + 1)) return LM_ERROR;
   std::vector<long long> rebased((size_t)S + 1);
   for (int s = 0; s <= S; ++s) rebased[s] = offsets[s] - offsets[0];
-  hipError_t e = hipMemcpy(u->offsets.ptr, rebased.data(), sizeof(long long) * rebased.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess && total) e = hipMemcpy(u->angles.ptr, angles + 3 * offsets[0], sizeof(double) * 3 * total, hipMemcpyHostToDevice);
-  if (e == hipSuccess && total) e = hipMemcpy(u->x.ptr, x + offsets[0], sizeof(double) * total, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    set_error("%s(): host->device copy failed: %s", who, hipGetErrorString(e));
-    return LM_ERROR;
-  }
-  return 0;
+  *d_offsets = h.in(rebased.data(), rebased.size());
+  *d_angles = h.in(angles + 3 * offsets[0], 3 * total);
+  *d_x = h.in(x + offsets[0], total);
 }
-static_assert(sizeof(long long) == sizeof(double), "the offsets travel in a block of doubles");
 }  // namespace
 
 int brdf_hip_fit_batch_packed(int method, int model, const double *angles, const double *x, const long long *offsets, int S, double *p,
                               const double *lb, const double *ub, int itmax, const double *opts, double *info, int *ret,
                               long long workspace_bytes) {
   const char *who = "brdf_hip_fit_batch_packed";
-  PackedFitArgs a = {method, model, angles, x, offsets, S, p, lb, ub, itmax, opts, nullptr, nullptr, workspace_bytes, nullptr};  // (host pointers: checked for null only)
+  PackedFitArgs a = {method, model, angles, x, offsets, S, p, lb, ub, itmax, opts, info, ret, workspace_bytes, nullptr};  // (host pointers: checked for null only)
   if (packed_fit_check(a, who) != 0 || check_host_offsets(who, offsets, S) != 0) return LM_ERROR;
-  PackedUpload u;
-  DevBuf d_p, d_info, d_ret;
-  if (upload_packed(who, angles, x, offsets, S, &u) != 0 || alloc_doubles(d_p, 3 * (size_t)S) || alloc_doubles(d_info, 10 * (size_t)S) ||
-      alloc_doubles(d_ret, ((size_t)S + 1) / 2 + 1))
-    return LM_ERROR;
-  hipError_t e = hipMemcpy(d_p.ptr, p, sizeof(double) * 3 * S, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    set_error("%s(): host->device copy failed: %s", who, hipGetErrorString(e));
-    return LM_ERROR;
-  }
-  a.d_angles = u.angles.ptr;
-  a.d_x = u.x.ptr;
-  a.d_offsets = u.d_offsets();
-  a.d_p = d_p.ptr;
-  a.d_info = d_info.ptr;
-  a.d_ret = reinterpret_cast<int *>(d_ret.ptr);
-  if (packed_fit_run(a, who) != 0) return LM_ERROR;
-  std::vector<int> host_ret((size_t)S);
-  e = hipStreamSynchronize(nullptr);
-  if (e == hipSuccess) e = hipMemcpy(p, d_p.ptr, sizeof(double) * 3 * S, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && info) e = hipMemcpy(info, d_info.ptr, sizeof(double) * 10 * S, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(host_ret.data(), a.d_ret, sizeof(int) * S, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) {
-    set_error("%s(): %s", who, hipGetErrorString(e));
-    return LM_ERROR;
-  }
-  int bad = 0;
-  for (int s = 0; s < S; ++s) {
-    bad += host_ret[s] < 0;
-    if (ret) ret[s] = host_ret[s];
-  }
-  return bad;
+  std::vector<int> own_ret(ret ? 0 : S);
+  if (!ret) ret = own_ret.data();
+  HostCall h(who);
+  upload_packed(h, angles, x, offsets, S, &a.d_angles, &a.d_x, &a.d_offsets);
+  a.d_p = h.inout(p, 3 * (size_t)S);
+  a.d_info = h.out(info, 10 * (size_t)S);
+  a.d_ret = h.out(ret, S);
+  if (h.failed() || packed_fit_run(a, who) != 0 || h.finish() != 0) return LM_ERROR;
+  return count_failed(ret, S);
 }
 
 int brdf_hip_fit_stats_batch_packed(int method, int model, const double *angles, const double *x, const long long *offsets, int S,
@@ -771,32 +625,13 @@ int brdf_hip_fit_stats_batch_packed(int method, int model, const double *angles,
   const char *who = "brdf_hip_fit_stats_batch_packed";
   PackedStatsArgs a = {method, model, angles, x, offsets, S, p, opts, covar, stats, rank, workspace_bytes, nullptr};  // (host pointers: checked for null only)
   if (packed_stats_check(a, who) != 0 || check_host_offsets(who, offsets, S) != 0) return LM_ERROR;
-  PackedUpload u;
-  DevBuf d_p, d_covar, d_stats, d_rank;
-  if (upload_packed(who, angles, x, offsets, S, &u) != 0 || alloc_doubles(d_p, 3 * (size_t)S) || (covar && alloc_doubles(d_covar, 9 * (size_t)S)) ||
-      (stats && alloc_doubles(d_stats, BRDF_STATS_SZ * (size_t)S)) || (rank && alloc_doubles(d_rank, ((size_t)S + 1) / 2 + 1)))
-    return LM_ERROR;
-  hipError_t e = hipMemcpy(d_p.ptr, p, sizeof(double) * 3 * S, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    set_error("%s(): host->device copy failed: %s", who, hipGetErrorString(e));
-    return LM_ERROR;
-  }
-  a.d_angles = u.angles.ptr;
-  a.d_x = u.x.ptr;
-  a.d_offsets = u.d_offsets();
-  a.d_p = d_p.ptr;
-  a.d_covar = d_covar.ptr;
-  a.d_stats = d_stats.ptr;
-  a.d_rank = reinterpret_cast<int *>(d_rank.ptr);
-  if (packed_stats_run(a, who) != 0) return LM_ERROR;
-  e = hipStreamSynchronize(nullptr);
-  if (e == hipSuccess && covar) e = hipMemcpy(covar, d_covar.ptr, sizeof(double) * 9 * S, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && stats) e = hipMemcpy(stats, d_stats.ptr, sizeof(double) * BRDF_STATS_SZ * S, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && rank) e = hipMemcpy(rank, d_rank.ptr, sizeof(int) * S, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) {
-    set_error("%s(): %s", who, hipGetErrorString(e));
-    return LM_ERROR;
-  }
+  HostCall h(who);
+  upload_packed(h, angles, x, offsets, S, &a.d_angles, &a.d_x, &a.d_offsets);
+  a.d_p = h.in(p, 3 * (size_t)S);
+  a.d_covar = h.out(covar, 9 * (size_t)S);
+  a.d_stats = h.out(stats, BRDF_STATS_SZ * (size_t)S);
+  a.d_rank = h.out(rank, S);
+  if (h.failed() || packed_stats_run(a, who) != 0 || h.finish() != 0) return LM_ERROR;
   return 0;
 }
 

@@ -330,23 +330,10 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
                          mask->v_min, mask->v_max, mask->cos_min, use1, use2, fit_counts.as<int>());
     CAP_OK(hipGetLastError());
   }
-  BatchFitArgs a;
-  a.d_counts = mask ? fit_counts.as<int>() : nullptr;
-  a.method = BRDF_METHOD_BC_DIF;  // brdfdata.cpp:1119
-  a.model = model;
-  a.d_angles = angles.as<double>();
-  a.d_x = x.as<double>();
-  a.S = (int)(3 * S);
-  a.n = L;
-  a.d_p = p.as<double>();
-  a.lb = lb;
-  a.ub = ub;
-  a.itmax = itmax;
-  a.opts = opts;
-  a.d_info = nullptr;
-  a.d_ret = ret.as<int>();
-  a.stream = stream;
-  if (batch_fit_enqueue(a) != 0) return kLmError;
+  // dlevmar_bc_dif: brdfdata.cpp:1119; no info; with a mask the fits are ragged
+  const BatchFitArgs a = {BRDF_METHOD_BC_DIF, model, angles.as<double>(), x.as<double>(), (int)(3 * S), L, p.as<double>(), lb, ub, itmax, opts, nullptr,
+                          ret.as<int>(), stream, mask ? fit_counts.as<int>() : nullptr};
+  if (batch_fit_enqueue(a, who) != 0) return kLmError;
   const int sb = (int)((3 * S + kCT - 1) / kCT);
   CAP_OK(sums.ensure(sizeof(double) * 3 * sb));
   hipLaunchKernelGGL(store_kernel, dim3(sb), dim3(kCT), 0, stream, p.as<double>(), face_s.as<int>(), last.as<long long>(), S,
@@ -362,22 +349,8 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
     CAP_OK(src_of_row.ensure(sizeof(int) * 3 * (size_t)nf));
     hipLaunchKernelGGL(stats_rows_kernel, dim3((3 * nf + kCT - 1) / kCT), dim3(kCT), 0, stream, last.as<long long>(), nf, src_of_row.as<int>());
     CAP_OK(hipGetLastError());
-    FitStatsArgs fs;
-    fs.method = a.method;
-    fs.model = model;
-    fs.d_angles = a.d_angles;
-    fs.d_x = a.d_x;
-    fs.S = a.S;
-    fs.n = L;
-    fs.d_p = a.d_p;
-    fs.opts = opts;
-    fs.d_covar = d_surface_covar;
-    fs.d_stats = d_surface_stats;
-    fs.d_rank = d_surface_rank;
-    fs.d_src = src_of_row.as<int>();
-    fs.d_counts = a.d_counts;
-    fs.rows = 3 * nf;
-    fs.stream = stream;
+    const FitStatsArgs fs = {a.method, model, a.d_angles, a.d_x, a.S, L, a.d_p, opts, d_surface_covar, d_surface_stats, d_surface_rank,
+                             src_of_row.as<int>(), 3 * nf, stream, a.d_counts};
     if (fit_stats_enqueue(fs, who) != 0) return kLmError;
   }
   std::vector<double> h_sums((size_t)3 * sb);

@@ -34,6 +34,9 @@ inline bool method_spec(int abi_method, MethodSpec *out) {
 
 #include <atomic>
 #include <cstring>
+#include <deque>
+#include <tuple>
+#include <vector>
 
 #include "batch_fit.h"
 #include "stream_fit.h"
@@ -137,6 +140,52 @@ struct DeviceBlock {
   template <class U>
   U *as() const { return reinterpret_cast<U *>(ptr); }
 };
+
+// ---- a batched call through host pointers -----------------------------------------------------------------------------------
+// Owns the call's device blocks.  in() uploads host[0, count), out() hands out device memory that finish() downloads into host,
+// inout() both; a null host pointer gives null and no block.  The first HIP error is worded as the entry `who` where it happens and
+// every later request gives null; finish() waits for the null stream once, then downloads in the order of the requests.
+class HostCall {
+ public:
+  explicit HostCall(const char *who) : who_(who) {}
+  template <class T>
+  const T *in(const T *host, size_t count) { return add<T>(host, nullptr, count); }
+  template <class T>
+  T *out(T *host, size_t count) { return add<T>(nullptr, host, count); }
+  template <class T>
+  T *inout(T *host, size_t count) { return add<T>(host, host, count); }
+  bool failed() const { return failed_; }
+  int finish();  // 0, or kLmError and the error text
+
+ private:
+  template <class T>
+  T *add(const T *up, T *down, size_t count) {
+    if (failed_ || (!up && !down)) return nullptr;
+    auto &blocks = std::get<std::deque<DeviceBlock<T>>>(blocks_);
+    blocks.emplace_back();
+    return static_cast<T *>(stage(blocks.back().ensure(count), blocks.back().ptr, up, down, count * sizeof(T)));
+  }
+  void *stage(hipError_t allocated, void *dev, const void *up, void *down, size_t bytes);
+  struct Download {
+    void *host;
+    const void *dev;
+    size_t bytes;
+  };
+  const char *who_;
+  bool failed_ = false;
+  std::vector<Download> downloads_;
+  std::tuple<std::deque<DeviceBlock<double>>, std::deque<DeviceBlock<int>>, std::deque<DeviceBlock<long long>>> blocks_;
+};
+
+// ---- what the batched entries refuse ------------------------------------------------------------------------------------------
+// (no HIP call; `who`: the entry that was called, as the text shows it)
+// an unknown model or method; otherwise *ms is the method's
+bool known_model_method(int model, int method, MethodSpec *ms, const char *who);
+// a lower bound above the upper one where the machine has a box: levmar's own refusal, lmbc_core.c:451-454
+bool box_refused(MethodSpec ms, const double *lb, const double *ub, const char *who);
+
+// a BigFit's (batch_fit.h) three plane prefixes [0, k) next to each other in `pack`, as a single fit reads them (k < stride: a ragged fit)
+int pack_plane_prefixes(const BigFit &f, DeviceBlock<double> &pack, hipStream_t stream);
 
 // ---- fast, then exact -----------------------------------------------------------------------------------------------------
 // Batched: launch(true, queue) enqueues the prepared-sample kernel, launch(false, queue + 1) its exact twin over the fits that

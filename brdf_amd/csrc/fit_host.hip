@@ -25,6 +25,50 @@ void set_bad_input_error(const char *who, int bad_input, int n, int m) {
   }
 }
 
+void *HostCall::stage(hipError_t e, void *dev, const void *up, void *down, size_t bytes) {
+  if (e != hipSuccess) {
+    set_error("%s(): hipMalloc(%zu bytes) failed: %s", who_, bytes, hipGetErrorString(e));
+  } else if (up && bytes && (e = hipMemcpy(dev, up, bytes, hipMemcpyHostToDevice)) != hipSuccess) {
+    set_error("%s(): host->device copy failed: %s", who_, hipGetErrorString(e));
+  }
+  failed_ = e != hipSuccess;
+  if (failed_) return nullptr;
+  if (down) downloads_.push_back({down, dev, bytes});
+  return dev;
+}
+
+int HostCall::finish() {
+  hipError_t e = hipStreamSynchronize(nullptr);
+  for (const Download &d : downloads_)
+    if (e == hipSuccess) e = hipMemcpy(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) return 0;
+  set_error("%s(): %s", who_, hipGetErrorString(e));
+  return kLmError;
+}
+
+bool known_model_method(int model, int method, MethodSpec *ms, const char *who) {
+  if (model >= 0 && model < MODEL_COUNT && method_spec(method, ms)) return true;
+  set_error("%s(): unknown model %d / method %d", who, model, method);
+  return false;
+}
+
+bool box_refused(MethodSpec ms, const double *lb, const double *ub, const char *who) {
+  if (ms.machine != kBcMachine || !lb || !ub) return false;
+  for (int i = 0; i < kM; ++i)
+    if (lb[i] > ub[i]) {
+      set_bad_input_error(who, 2, 0, kM);
+      return true;
+    }
+  return false;
+}
+
+int pack_plane_prefixes(const BigFit &f, DeviceBlock<double> &pack, hipStream_t stream) {
+  HIP_OK(pack.ensure(3 * (size_t)f.stride));
+  for (int pl = 0; pl < 3; ++pl)
+    HIP_OK(hipMemcpyAsync(pack.ptr + (size_t)pl * f.k, f.d_angles + (size_t)pl * f.stride, sizeof(double) * f.k, hipMemcpyDeviceToDevice, stream));
+  return 0;
+}
+
 void warn_start_projected(int i, double from, double to) {
   fprintf(stderr, "Warning: component %d of starting point not feasible in dlevmar_bc_dif()! [%g projected to %g]\n", i, from, to);
 }

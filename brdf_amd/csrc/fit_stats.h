@@ -3,6 +3,7 @@
 // function of (angles, x, p, method, opts[4]) and does not care who fitted p.
 #pragma once
 
+#include "batch_fit.h"
 #include "device_common.h"
 
 namespace brdf {
@@ -31,5 +32,8 @@ struct FitStatsArgs {
 // argument check (no HIP call) and enqueue; `who` names the entry point in error texts.  Asynchronous on a.stream.
 int fit_stats_check(const FitStatsArgs &a, const char *who);
 int fit_stats_enqueue(const FitStatsArgs &a, const char *who);
+// a fit above 4096 samples whose planes lie next to each other at `planes` (b.k apart): the uniform pass with S = 1, n = b.k at row b.row
+// of a's p, straight into row b.row of a's covar / stats / rank; method, model, opts and stream are a's
+int big_fit_stats_enqueue(const FitStatsArgs &a, const BigFit &b, const double *planes, const char *who);
 
 }  // namespace brdf

@@ -341,10 +341,7 @@ bool stats_fast_path() { return switch_on(kSwStatsFast); }
 
 int fit_stats_check(const FitStatsArgs &a, const char *who) {
   MethodSpec ms;
-  if (a.model < 0 || a.model >= MODEL_COUNT || !method_spec(a.method, &ms)) {
-    set_error("%s(): unknown model %d / method %d", who, a.model, a.method);
-    return kLmError;
-  }
+  if (!known_model_method(a.model, a.method, &ms, who)) return kLmError;
   if (!a.d_angles || !a.d_x || !a.d_p) {
     set_error("%s(): null angles, x or p", who);
     return kLmError;
@@ -360,11 +357,34 @@ int fit_stats_check(const FitStatsArgs &a, const char *who) {
   return 0;
 }
 
-// ragged statistics of fits with a stride above 4096: one after the other.  A fit of k >= 3 samples is the uniform pass with S = 1,
-// n = k over its three plane prefixes packed next to each other; a refused one (k < 3) takes the ragged workgroup kernel, which
-// reads the first k samples of the row where it lies.
 namespace {
 int stats_launches(const FitStatsArgs &a, const char *who, bool refused_large);
+
+// one fit of the batch: S = 1, its row of p and of the outputs (angles, x, n and the counts are the caller's to set)
+FitStatsArgs row_of(const FitStatsArgs &a, long long row) {
+  FitStatsArgs f = a;
+  f.S = 1;
+  f.d_p = a.d_p + row * kM;
+  f.d_covar = a.d_covar ? a.d_covar + row * kM * kM : nullptr;
+  f.d_stats = a.d_stats ? a.d_stats + row * kStatsSz : nullptr;
+  f.d_rank = a.d_rank ? a.d_rank + row : nullptr;
+  return f;
+}
+}  // namespace
+
+int big_fit_stats_enqueue(const FitStatsArgs &a, const BigFit &b, const double *planes, const char *who) {
+  FitStatsArgs f = row_of(a, b.row);
+  f.d_angles = planes;
+  f.d_x = b.d_x;
+  f.n = b.k;
+  f.d_counts = nullptr;
+  return fit_stats_enqueue(f, who);
+}
+
+// ragged statistics of fits with a stride above 4096: one after the other.  A fit of k >= 3 samples is the uniform pass on its three
+// plane prefixes packed next to each other; a refused one (k < 3) takes the ragged workgroup kernel, which reads the first k samples
+// of the row where it lies.
+namespace {
 int stats_of_large_ragged(const FitStatsArgs &a, const char *who) {
   if (a.d_src) {
     set_error("%s(): row indirection with per-fit counts is limited to n <= %d", who, kBlockMaxN);
@@ -373,33 +393,19 @@ int stats_of_large_ragged(const FitStatsArgs &a, const char *who) {
   std::vector<int> counts((size_t)a.S);
   STATS_OK(hipMemcpyAsync(counts.data(), a.d_counts, sizeof(int) * counts.size(), hipMemcpyDeviceToHost, a.stream));
   STATS_OK(hipStreamSynchronize(a.stream));
-  int kmax = 0;
-  for (int &k : counts) {
-    if (k < 0 || k > a.n) k = 0;
-    if (k > kmax) kmax = k;
-  }
   DeviceBlock<double> pack;
-  if (kmax >= kM) STATS_OK(pack.ensure(3 * (size_t)kmax));
   for (int s = 0; s < a.S; ++s) {
-    const int k = counts[s];
-    FitStatsArgs f = a;
-    f.S = 1;
-    f.d_angles = a.d_angles + (size_t)s * 3 * a.n;
-    f.d_x = a.d_x + (size_t)s * a.n;
-    f.d_p = a.d_p + (size_t)s * kM;
-    f.d_covar = a.d_covar ? a.d_covar + (size_t)s * kM * kM : nullptr;
-    f.d_stats = a.d_stats ? a.d_stats + (size_t)s * kStatsSz : nullptr;
-    f.d_rank = a.d_rank ? a.d_rank + s : nullptr;
+    const int k = (counts[s] < 0 || counts[s] > a.n) ? 0 : counts[s];
+    const BigFit b = {a.d_angles + (size_t)s * 3 * a.n, a.d_x + (size_t)s * a.n, k, a.n, s};
     if (k >= kM) {
-      for (int pl = 0; pl < 3; ++pl)
-        STATS_OK(hipMemcpyAsync(pack.ptr + (size_t)pl * k, f.d_angles + (size_t)pl * a.n, sizeof(double) * k, hipMemcpyDeviceToDevice, a.stream));
-      f.d_angles = pack.ptr;
-      f.n = k;
-      f.d_counts = nullptr;
+      if (pack_plane_prefixes(b, pack, a.stream) != 0 || big_fit_stats_enqueue(a, b, pack.ptr, who) != 0) return kLmError;
     } else {
+      FitStatsArgs f = row_of(a, s);
+      f.d_angles = b.d_angles;
+      f.d_x = b.d_x;
       f.d_counts = a.d_counts + s;
+      if (stats_launches(f, who, true) != 0) return kLmError;
     }
-    if (stats_launches(f, who, k < kM) != 0) return kLmError;
   }
   STATS_OK(hipStreamSynchronize(a.stream));  // (the packed planes are about to go away)
   return 0;

@@ -151,10 +151,7 @@ int brdf_hip_fit_batch_multi(int method, int model, const double *angles, const 
     return LM_ERROR;
   }
   MethodSpec ms;
-  if (model < 0 || model >= MODEL_COUNT || !method_spec(method, &ms)) {
-    set_error("brdf_hip_fit_batch_multi(): unknown model %d / method %d", model, method);
-    return LM_ERROR;
-  }
+  if (!known_model_method(model, method, &ms, "brdf_hip_fit_batch_multi")) return LM_ERROR;
   if (devices && (ndev < 1 || ndev > kMaxDeviceList)) {
     set_error("brdf_hip_fit_batch_multi(): ndev = %d, the device list needs 1 to %d entries", ndev, kMaxDeviceList);
     return LM_ERROR;

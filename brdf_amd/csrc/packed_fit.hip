@@ -8,7 +8,7 @@
 //             d_counts), a scatter of the results to the caller's rows.  The stride is never above the class bound, so the class's own
 //             kernel is chosen, and inside its class a ragged fit has the bytes of the uniform call at n = count.
 //   class 5   zero copy: a fit's segment already is the single-fit layout; stream_fit_run with n = k_s on the caller's memory (the
-//             path of batch_of_large_fits), one download of the starting points before the loop, one upload of the results after it.
+//             loop of the uniform call above 4096 samples, big_fits_run), one download of the starting points before the loop, one upload of the results after it.
 //
 // The phases are ordered by kernel boundaries only.  Atomics: integer adds and maxima on counters whose order cannot show.
 #include <climits>
@@ -336,23 +336,69 @@ bool common_args_bad(const void *angles, const void *x, const void *offsets, con
   return false;
 }
 
+// what the fit and the statistics call share
+struct PackedIn {
+  const double *angles, *x, *p;
+  const long long *off;
+  long long workspace_bytes;
+  hipStream_t stream;
+};
+// the results of a chunk: two double columns and one int column of its workspace, and the caller's arrays their rows go to
+struct Columns {
+  double *Workspace::*src0, *Workspace::*src1;
+  double *dst0, *dst1;  // null: not wanted
+  int w0, w1;
+  int *idst;  // from Workspace::wi
+};
+
+// Classes 0..4 of the plan: per class the stride, the chunk size and one workspace; per chunk gather, enqueue(w, fits, stride) -- the
+// caller's ragged launch on the padded rows --, scatter.
+template <class Enqueue>
+int run_small_classes(const Plan &pl, const PackedIn &in, const Columns &out, const char *who, Enqueue enqueue) {
+  for (int cls = 0; cls < kPackedLargeClass; ++cls) {
+    if (pl.fits[cls] == 0) continue;
+    const int stride = packed_stride(pl.largest[cls]);
+    long long chunk = packed_chunk_fits(in.workspace_bytes, stride);
+    if (chunk > pl.fits[cls]) chunk = pl.fits[cls];
+    g_last.fits[cls] = pl.fits[cls];
+    g_last.stride[cls] = stride;
+    Workspace w;
+    if (carve(&w, chunk, stride, in.stream, who) != 0) return kLmError;
+    for (long long at = 0; at < pl.fits[cls]; at += chunk) {
+      const int fits = (int)(pl.fits[cls] - at < chunk ? pl.fits[cls] - at : chunk);
+      const int *perm = pl.perm_of(cls) + at;
+      const GatherCtx g = {in.angles, in.x, in.p, in.off, perm, fits, stride, w.wa, w.wx, w.wp, w.wc};
+      if (gather_enqueue(cls, g, in.stream, who) != 0 || enqueue(w, fits, stride) != 0) return kLmError;
+      const ScatterCtx s = {perm, fits, w.*out.src0, w.*out.src1, out.dst0, out.dst1, out.w0, out.w1, w.wi, out.idst};
+      if (scatter_enqueue(s, in.stream, who) != 0) return kLmError;
+      ++g_last.chunks[cls];
+    }
+  }
+  return 0;
+}
+
+// class 5 on the host (one launch, one download), as the fits the single-fit path runs: a segment already is its layout.  row_is_fit:
+// a fit's row is its index in the batch (the statistics write there), otherwise its place in the class
+int big_fits_of(const Plan &pl, const PackedIn &in, bool row_is_fit, std::vector<LargeFit> *large, std::vector<BigFit> *big, const char *who) {
+  if (download_large(pl, in.off, in.p, in.stream, large, who) != 0) return kLmError;
+  for (size_t j = 0; j < large->size(); ++j) {
+    const LargeFit &f = (*large)[j];
+    big->push_back({in.angles + 3 * f.off, in.x + f.off, (int)f.k, (int)f.k, row_is_fit ? f.s : (long long)j});
+  }
+  g_last.fits[kPackedLargeClass] = g_last.chunks[kPackedLargeClass] = (int)large->size();
+  g_last.stride[kPackedLargeClass] = pl.largest[kPackedLargeClass];
+  return 0;
+}
+
 }  // namespace
 
 PackedLastStats packed_last_stats() { return g_last; }
 
 int packed_fit_check(const PackedFitArgs &a, const char *who) {
   MethodSpec ms;
-  if (a.model < 0 || a.model >= MODEL_COUNT || !method_spec(a.method, &ms)) {
-    set_error("%s(): unknown model %d / method %d", who, a.model, a.method);
+  if (!known_model_method(a.model, a.method, &ms, who) || common_args_bad(a.d_angles, a.d_x, a.d_offsets, a.d_p, a.S, a.workspace_bytes, who) ||
+      box_refused(ms, a.lb, a.ub, who))  // (the whole call, its fits above 4096 samples included: batch_fit_check lets those pass)
     return kLmError;
-  }
-  if (common_args_bad(a.d_angles, a.d_x, a.d_offsets, a.d_p, a.S, a.workspace_bytes, who)) return kLmError;
-  if (ms.machine == kBcMachine && a.lb && a.ub)
-    for (int i = 0; i < kM; ++i)
-      if (a.lb[i] > a.ub[i]) {  // lmbc_core.c:451-454
-        set_bad_input_error(who, 2, 0, kM);
-        return kLmError;
-      }
   return 0;
 }
 
@@ -362,62 +408,27 @@ int packed_fit_run(const PackedFitArgs &a, const char *who) {
   g_last = PackedLastStats{};
   Plan pl;
   if (make_plan(a.d_offsets, a.S, a.stream, &pl, who) != 0) return kLmError;
-  for (int cls = 0; cls < kPackedLargeClass; ++cls) {
-    if (pl.fits[cls] == 0) continue;
-    const int stride = packed_stride(pl.largest[cls]);
-    long long chunk = packed_chunk_fits(a.workspace_bytes, stride);
-    if (chunk > pl.fits[cls]) chunk = pl.fits[cls];
-    g_last.fits[cls] = pl.fits[cls];
-    g_last.stride[cls] = stride;
-    Workspace w;
-    if (carve(&w, chunk, stride, a.stream, who) != 0) return kLmError;
-    for (long long at = 0; at < pl.fits[cls]; at += chunk) {
-      const int fits = (int)(pl.fits[cls] - at < chunk ? pl.fits[cls] - at : chunk);
-      const int *perm = pl.perm_of(cls) + at;
-      const GatherCtx g = {a.d_angles, a.d_x, a.d_p, a.d_offsets, perm, fits, stride, w.wa, w.wx, w.wp, w.wc};
-      if (gather_enqueue(cls, g, a.stream, who) != 0) return kLmError;
-      BatchFitArgs b;
-      b.method = a.method;
-      b.model = a.model;
-      b.d_angles = w.wa;
-      b.d_x = w.wx;
-      b.S = fits;
-      b.n = stride;
-      b.d_p = w.wp;
-      b.lb = a.lb;
-      b.ub = a.ub;
-      b.itmax = a.itmax;
-      b.opts = a.opts;
-      b.d_info = w.wd0;
-      b.d_ret = w.wi;
-      b.stream = a.stream;
-      b.d_counts = w.wc;
-      if (batch_fit_enqueue(b) != 0) return kLmError;
-      const ScatterCtx s = {perm, fits, w.wp, w.wd0, a.d_p, a.d_info, kM, kInfoSz, w.wi, a.d_ret};
-      if (scatter_enqueue(s, a.stream, who) != 0) return kLmError;
-      ++g_last.chunks[cls];
-    }
-  }
+  const PackedIn in = {a.d_angles, a.d_x, a.d_p, a.d_offsets, a.workspace_bytes, a.stream};
+  const Columns out = {&Workspace::wp, &Workspace::wd0, a.d_p, a.d_info, kM, kInfoSz, a.d_ret};
+  if (run_small_classes(pl, in, out, who, [&](const Workspace &w, int fits, int stride) {
+        const BatchFitArgs b = {a.method, a.model, w.wa, w.wx, fits, stride, w.wp, a.lb, a.ub, a.itmax, a.opts, w.wd0, w.wi, a.stream, w.wc};
+        return batch_fit_enqueue(b, who);
+      }) != 0)
+    return kLmError;
   const int n5 = (int)pl.fits[kPackedLargeClass];
   if (n5 == 0) return 0;
   // class 5: the fits run where they lie, one after the other, each spread over the chip (synchronous, as in the uniform call)
-  MethodSpec ms;
-  (void)method_spec(a.method, &ms);
   std::vector<LargeFit> large;
-  if (download_large(pl, a.d_offsets, a.d_p, a.stream, &large, who) != 0) return kLmError;
+  std::vector<BigFit> big;
+  if (big_fits_of(pl, in, false, &large, &big, who) != 0) return kLmError;
   // the results, laid out as the scatter reads them: p[n5][3], info[n5][10], then ret[n5]
   std::vector<double> res((size_t)n5 * (kM + kInfoSz) + ((size_t)n5 + 1) / 2);
   double *hp = res.data(), *hinfo = hp + (size_t)n5 * kM;
   int *hret = reinterpret_cast<int *>(hinfo + (size_t)n5 * kInfoSz);
-  for (int j = 0; j < n5; ++j) {
-    const LargeFit &f = large[j];
-    for (int i = 0; i < kM; ++i) hp[(size_t)j * kM + i] = f.p[i];
-    const StreamFitArgs sf = stream_fit_args(ms, a.model, a.d_angles + 3 * f.off, a.d_x + f.off, (int)f.k, hp + (size_t)j * kM, a.lb, a.ub, nullptr,
-                                             a.itmax, a.opts, hinfo + (size_t)j * kInfoSz, nullptr, a.stream);
-    hret[j] = stream_fit_run(sf);
-  }
-  g_last.fits[kPackedLargeClass] = g_last.chunks[kPackedLargeClass] = n5;
-  g_last.stride[kPackedLargeClass] = pl.largest[kPackedLargeClass];
+  for (int j = 0; j < n5; ++j)
+    for (int i = 0; i < kM; ++i) hp[(size_t)j * kM + i] = large[j].p[i];
+  const BatchFitArgs b = {a.method, a.model, a.d_angles, a.d_x, n5, 0, nullptr, a.lb, a.ub, a.itmax, a.opts, nullptr, nullptr, a.stream};
+  if (big_fits_run(b, big.data(), n5, hp, hinfo, hret) != 0) return kLmError;
   AsyncBuf d;
   PACKED_OK(d.get(sizeof(double) * res.size(), a.stream));
   PACKED_OK(hipMemcpyAsync(d.ptr, res.data(), sizeof(double) * res.size(), hipMemcpyHostToDevice, a.stream));
@@ -431,11 +442,8 @@ int packed_fit_run(const PackedFitArgs &a, const char *who) {
 
 int packed_stats_check(const PackedStatsArgs &a, const char *who) {
   MethodSpec ms;
-  if (a.model < 0 || a.model >= MODEL_COUNT || !method_spec(a.method, &ms)) {
-    set_error("%s(): unknown model %d / method %d", who, a.model, a.method);
+  if (!known_model_method(a.model, a.method, &ms, who) || common_args_bad(a.d_angles, a.d_x, a.d_offsets, a.d_p, a.S, a.workspace_bytes, who))
     return kLmError;
-  }
-  if (common_args_bad(a.d_angles, a.d_x, a.d_offsets, a.d_p, a.S, a.workspace_bytes, who)) return kLmError;
   if (!a.d_covar && !a.d_stats && !a.d_rank) {
     set_error("%s(): covar, stats and rank are all NULL: nothing to compute", who);
     return kLmError;
@@ -449,60 +457,21 @@ int packed_stats_run(const PackedStatsArgs &a, const char *who) {
   g_last = PackedLastStats{};
   Plan pl;
   if (make_plan(a.d_offsets, a.S, a.stream, &pl, who) != 0) return kLmError;
-  FitStatsArgs f;
-  f.method = a.method;
-  f.model = a.model;
-  f.opts = a.opts;
-  f.stream = a.stream;
-  for (int cls = 0; cls < kPackedLargeClass; ++cls) {
-    if (pl.fits[cls] == 0) continue;
-    const int stride = packed_stride(pl.largest[cls]);
-    long long chunk = packed_chunk_fits(a.workspace_bytes, stride);
-    if (chunk > pl.fits[cls]) chunk = pl.fits[cls];
-    g_last.fits[cls] = pl.fits[cls];
-    g_last.stride[cls] = stride;
-    Workspace w;
-    if (carve(&w, chunk, stride, a.stream, who) != 0) return kLmError;
-    for (long long at = 0; at < pl.fits[cls]; at += chunk) {
-      const int fits = (int)(pl.fits[cls] - at < chunk ? pl.fits[cls] - at : chunk);
-      const int *perm = pl.perm_of(cls) + at;
-      const GatherCtx g = {a.d_angles, a.d_x, a.d_p, a.d_offsets, perm, fits, stride, w.wa, w.wx, w.wp, w.wc};
-      if (gather_enqueue(cls, g, a.stream, who) != 0) return kLmError;
-      f.d_angles = w.wa;
-      f.d_x = w.wx;
-      f.S = fits;
-      f.n = stride;
-      f.d_p = w.wp;
-      f.d_covar = w.wd0;
-      f.d_stats = w.wd1;
-      f.d_rank = w.wi;
-      f.d_counts = w.wc;
-      if (fit_stats_enqueue(f, who) != 0) return kLmError;
-      const ScatterCtx s = {perm, fits, w.wd0, w.wd1, a.d_covar, a.d_stats, kM * kM, kStatsSz, w.wi, a.d_rank};
-      if (scatter_enqueue(s, a.stream, who) != 0) return kLmError;
-      ++g_last.chunks[cls];
-    }
-  }
-  const int n5 = (int)pl.fits[kPackedLargeClass];
-  if (n5 == 0) return 0;
+  const PackedIn in = {a.d_angles, a.d_x, a.d_p, a.d_offsets, a.workspace_bytes, a.stream};
+  const Columns out = {&Workspace::wd0, &Workspace::wd1, a.d_covar, a.d_stats, kM * kM, kStatsSz, a.d_rank};
+  if (run_small_classes(pl, in, out, who, [&](const Workspace &w, int fits, int stride) {
+        const FitStatsArgs f = {a.method, a.model, w.wa, w.wx, fits, stride, w.wp, a.opts, w.wd0, w.wd1, w.wi, nullptr, 0, a.stream, w.wc};
+        return fit_stats_enqueue(f, who);
+      }) != 0)
+    return kLmError;
+  if (pl.fits[kPackedLargeClass] == 0) return 0;
   // class 5: the uniform pass with S = 1 on the segment, results straight into the caller's rows
   std::vector<LargeFit> large;
-  if (download_large(pl, a.d_offsets, a.d_p, a.stream, &large, who) != 0) return kLmError;
-  f.d_counts = nullptr;
-  f.S = 1;
-  for (int j = 0; j < n5; ++j) {
-    const LargeFit &l = large[j];
-    f.d_angles = a.d_angles + 3 * l.off;
-    f.d_x = a.d_x + l.off;
-    f.n = (int)l.k;
-    f.d_p = a.d_p + (size_t)l.s * kM;
-    f.d_covar = a.d_covar ? a.d_covar + (size_t)l.s * kM * kM : nullptr;
-    f.d_stats = a.d_stats ? a.d_stats + (size_t)l.s * kStatsSz : nullptr;
-    f.d_rank = a.d_rank ? a.d_rank + l.s : nullptr;
-    if (fit_stats_enqueue(f, who) != 0) return kLmError;
-  }
-  g_last.fits[kPackedLargeClass] = g_last.chunks[kPackedLargeClass] = n5;
-  g_last.stride[kPackedLargeClass] = pl.largest[kPackedLargeClass];
+  std::vector<BigFit> big;
+  if (big_fits_of(pl, in, true, &large, &big, who) != 0) return kLmError;
+  const FitStatsArgs rows = {a.method, a.model, a.d_angles, a.d_x, a.S, 0, a.d_p, a.opts, a.d_covar, a.d_stats, a.d_rank, nullptr, 0, a.stream};
+  for (const BigFit &b : big)
+    if (big_fit_stats_enqueue(rows, b, b.d_angles, who) != 0) return kLmError;
   return 0;
 }
 

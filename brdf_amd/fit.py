@@ -6,7 +6,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import D, ExtraData, last_error, lib
+from ._lib import D, I, ExtraData, last_error, lib
 
 MODEL_PHONG, MODEL_BLINN_PHONG, MODEL_WARD = 0, 1, 2
 METHOD_DIF, METHOD_BC_DIF, METHOD_BC_DER, METHOD_DER = 0, 1, 2, 3  # 2 / 3: dlevmar_bc_der / dlevmar_der with the analytic Jacobian
@@ -30,6 +30,10 @@ def _dptr(a: np.ndarray | None):
     return None if a is None else a.ctypes.data_as(D)
 
 
+def _iptr(a: np.ndarray | None):
+    return None if a is None else a.ctypes.data_as(I)
+
+
 def _f64(v, size):
     if v is None:
         return None
@@ -40,6 +44,23 @@ def _f64(v, size):
 
 def _stream_handle(torch):
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+_STREAM = object()  # among _call's arguments: the current stream of the call's device
+
+
+def _call(name: str, device, *args) -> None:
+    """lib.<name>(*args) with `device` current (None: a host-pointer entry, no device scope); a non-zero return raises RuntimeError
+    with the library's error text."""
+    if device is None:
+        rc = getattr(lib, name)(*args)
+    else:
+        import torch
+        with torch.cuda.device(device):
+            stream = _stream_handle(torch)
+            rc = getattr(lib, name)(*(stream if a is _STREAM else a for a in args))
+    if rc != 0:
+        raise RuntimeError(f"{name} failed: {last_error()}")
 
 
 # brdf_hip_fit_dev once more, with plain addresses for its pointer arguments: ndarray.ctypes.data_as() costs ~3 us per pointer and a
@@ -175,19 +196,9 @@ def fit_batch(method: int, model: int, angles, x, p0, *, lb=None, ub=None, itmax
     lb_a, ub_a, op_a = _f64(lb, 3), _f64(ub, 3), _f64(opts, 5)
     if counts is not None:
         counts = _counts_arg(counts, S, x.device, torch)
-        with torch.cuda.device(x.device):
-            rc = lib.brdf_hip_fit_batch_ragged_dev(method, model, angles.data_ptr(), x.data_ptr(), counts.data_ptr(), S, n, p.data_ptr(),
-                                                   _dptr(lb_a), _dptr(ub_a), itmax, _dptr(op_a), info.data_ptr(), ret.data_ptr(),
-                                                   _stream_handle(torch))
-        if rc != 0:
-            raise RuntimeError(f"brdf_hip_fit_batch_ragged_dev failed: {last_error()}")
-        return p, info, ret
-    with torch.cuda.device(x.device):
-        rc = lib.brdf_hip_fit_batch_dev(method, model, angles.data_ptr(), x.data_ptr(), S, n, p.data_ptr(), _dptr(lb_a),
-                                        _dptr(ub_a), itmax, _dptr(op_a), info.data_ptr(), ret.data_ptr(),
-                                        _stream_handle(torch))
-    if rc != 0:
-        raise RuntimeError(f"brdf_hip_fit_batch_dev failed: {last_error()}")
+    # (null counts: the uniform call, include/brdf_levmar.h)
+    _call("brdf_hip_fit_batch_ragged_dev", x.device, method, model, angles.data_ptr(), x.data_ptr(), None if counts is None else counts.data_ptr(),
+          S, n, p.data_ptr(), _dptr(lb_a), _dptr(ub_a), itmax, _dptr(op_a), info.data_ptr(), ret.data_ptr(), _STREAM)
     return p, info, ret
 
 
@@ -197,6 +208,15 @@ class FitStats:
     covar: object  # [S,3,3]  sumsq/(n-3) * inverse(J^T J), J at p
     stats: object  # [S,8]    sumsq, R2, sd[0..2], rho01, rho02, rho12
     rank: object   # [S] int32: 3, or 0 where the covariance could not be formed (covar and its six derived values are 0)
+
+
+def _zero_stats(lead: tuple, device=None) -> FitStats:
+    """zeroed covar [*lead,3,3], stats [*lead,8] and rank [*lead]: CUDA tensors on `device`, or numpy arrays (None)"""
+    if device is None:
+        return FitStats(np.zeros(lead + (3, 3)), np.zeros(lead + (8,)), np.zeros(lead, dtype=np.int32))
+    import torch
+    return FitStats(torch.zeros(lead + (3, 3), dtype=torch.float64, device=device), torch.zeros(lead + (8,), dtype=torch.float64, device=device),
+                    torch.zeros(lead, dtype=torch.int32, device=device))
 
 
 def fit_stats_batch(method: int, model: int, angles, x, p, *, opts=None, counts=None) -> FitStats:
@@ -214,20 +234,13 @@ def fit_stats_batch(method: int, model: int, angles, x, p, *, opts=None, counts=
         _require(x.ndim == 2, "x must be [S, n]")
         S, n = x.shape
         _require(angles.shape == (S, 3, n) and p.shape == (S, 3), "angles must be [S, 3, n], p [S, 3]")
-        covar, stats, rank = np.zeros((S, 3, 3)), np.zeros((S, 8)), np.zeros(S, dtype=np.int32)
         if counts is not None:
             counts = np.ascontiguousarray(counts, dtype=np.int32)
             _require(counts.shape == (S,), "counts must be [S]")
-            rc = lib.brdf_hip_fit_stats_batch_ragged(method, model, _dptr(angles), _dptr(x), counts.ctypes.data_as(C.POINTER(C.c_int)), S, n,
-                                                     _dptr(p), _dptr(op_a), _dptr(covar), _dptr(stats), rank.ctypes.data_as(C.POINTER(C.c_int)))
-            if rc != 0:
-                raise RuntimeError(f"brdf_hip_fit_stats_batch_ragged failed: {last_error()}")
-            return FitStats(covar, stats, rank)
-        rc = lib.brdf_hip_fit_stats_batch(method, model, _dptr(angles), _dptr(x), S, n, _dptr(p), _dptr(op_a), _dptr(covar),
-                                          _dptr(stats), rank.ctypes.data_as(C.POINTER(C.c_int)))
-        if rc != 0:
-            raise RuntimeError(f"brdf_hip_fit_stats_batch failed: {last_error()}")
-        return FitStats(covar, stats, rank)
+        st = _zero_stats((S,))
+        _call("brdf_hip_fit_stats_batch_ragged", None, method, model, _dptr(angles), _dptr(x), _iptr(counts), S, n, _dptr(p), _dptr(op_a),
+              _dptr(st.covar), _dptr(st.stats), _iptr(st.rank))
+        return st
     import torch
     _require(angles.is_cuda and x.is_cuda and p.is_cuda and angles.device == x.device == p.device, "angles, x, p: CUDA tensors on one device")
     _require(angles.dtype == torch.float64 and x.dtype == torch.float64 and p.dtype == torch.float64, "angles, x, p: float64")  # the kernels read raw doubles
@@ -235,23 +248,12 @@ def fit_stats_batch(method: int, model: int, angles, x, p, *, opts=None, counts=
     S, n = x.shape
     _require(tuple(angles.shape) == (S, 3, n) and tuple(p.shape) == (S, 3), "angles must be [S, 3, n], p [S, 3]")
     angles, x, p = angles.contiguous(), x.contiguous(), p.contiguous()
-    covar = torch.zeros((S, 3, 3), dtype=torch.float64, device=x.device)
-    stats = torch.zeros((S, 8), dtype=torch.float64, device=x.device)
-    rank = torch.zeros((S,), dtype=torch.int32, device=x.device)
     if counts is not None:
         counts = _counts_arg(counts, S, x.device, torch)
-        with torch.cuda.device(x.device):
-            rc = lib.brdf_hip_fit_stats_batch_ragged_dev(method, model, angles.data_ptr(), x.data_ptr(), counts.data_ptr(), S, n, p.data_ptr(),
-                                                         _dptr(op_a), covar.data_ptr(), stats.data_ptr(), rank.data_ptr(), _stream_handle(torch))
-        if rc != 0:
-            raise RuntimeError(f"brdf_hip_fit_stats_batch_ragged_dev failed: {last_error()}")
-        return FitStats(covar, stats, rank)
-    with torch.cuda.device(x.device):
-        rc = lib.brdf_hip_fit_stats_batch_dev(method, model, angles.data_ptr(), x.data_ptr(), S, n, p.data_ptr(), _dptr(op_a),
-                                              covar.data_ptr(), stats.data_ptr(), rank.data_ptr(), _stream_handle(torch))
-    if rc != 0:
-        raise RuntimeError(f"brdf_hip_fit_stats_batch_dev failed: {last_error()}")
-    return FitStats(covar, stats, rank)
+    st = _zero_stats((S,), x.device)
+    _call("brdf_hip_fit_stats_batch_ragged_dev", x.device, method, model, angles.data_ptr(), x.data_ptr(), None if counts is None else counts.data_ptr(),
+          S, n, p.data_ptr(), _dptr(op_a), st.covar.data_ptr(), st.stats.data_ptr(), st.rank.data_ptr(), _STREAM)
+    return st
 
 
 def pack_samples(angles, x, counts):
@@ -305,12 +307,8 @@ def fit_batch_packed(method: int, model: int, angles, x, offsets, p0, *, lb=None
     info = torch.zeros((S, 10), dtype=torch.float64, device=x.device)
     ret = torch.zeros((S,), dtype=torch.int32, device=x.device)
     lb_a, ub_a, op_a = _f64(lb, 3), _f64(ub, 3), _f64(opts, 5)
-    with torch.cuda.device(x.device):
-        rc = lib.brdf_hip_fit_batch_packed_dev(method, model, angles.data_ptr(), x.data_ptr(), offsets.data_ptr(), S, p.data_ptr(), _dptr(lb_a),
-                                               _dptr(ub_a), itmax, _dptr(op_a), info.data_ptr(), ret.data_ptr(), int(workspace_bytes),
-                                               _stream_handle(torch))
-    if rc != 0:
-        raise RuntimeError(f"brdf_hip_fit_batch_packed_dev failed: {last_error()}")
+    _call("brdf_hip_fit_batch_packed_dev", x.device, method, model, angles.data_ptr(), x.data_ptr(), offsets.data_ptr(), S, p.data_ptr(), _dptr(lb_a),
+          _dptr(ub_a), itmax, _dptr(op_a), info.data_ptr(), ret.data_ptr(), int(workspace_bytes), _STREAM)
     return p, info, ret
 
 
@@ -320,16 +318,10 @@ def fit_stats_batch_packed(method: int, model: int, angles, x, offsets, p, *, op
     import torch
     angles, x, offsets, p = _packed_args(angles, x, offsets, p, validate, torch)
     S = offsets.numel() - 1
-    covar = torch.zeros((S, 3, 3), dtype=torch.float64, device=x.device)
-    stats = torch.zeros((S, 8), dtype=torch.float64, device=x.device)
-    rank = torch.zeros((S,), dtype=torch.int32, device=x.device)
-    op_a = _f64(opts, 5)
-    with torch.cuda.device(x.device):
-        rc = lib.brdf_hip_fit_stats_batch_packed_dev(method, model, angles.data_ptr(), x.data_ptr(), offsets.data_ptr(), S, p.data_ptr(), _dptr(op_a),
-                                                     covar.data_ptr(), stats.data_ptr(), rank.data_ptr(), int(workspace_bytes), _stream_handle(torch))
-    if rc != 0:
-        raise RuntimeError(f"brdf_hip_fit_stats_batch_packed_dev failed: {last_error()}")
-    return FitStats(covar, stats, rank)
+    st = _zero_stats((S,), x.device)
+    _call("brdf_hip_fit_stats_batch_packed_dev", x.device, method, model, angles.data_ptr(), x.data_ptr(), offsets.data_ptr(), S, p.data_ptr(),
+          _dptr(_f64(opts, 5)), st.covar.data_ptr(), st.stats.data_ptr(), st.rank.data_ptr(), int(workspace_bytes), _STREAM)
+    return st
 
 
 def last_packed_stats() -> list:
@@ -388,10 +380,7 @@ def model_eval(model: int, angles, p):
     n = angles.numel() // 3
     hx = torch.empty(n, dtype=torch.float64, device=angles.device)
     pa = _f64(p, 3)
-    with torch.cuda.device(angles.device):
-        rc = lib.brdf_hip_model_eval_dev(model, angles.data_ptr(), n, _dptr(pa), hx.data_ptr(), _stream_handle(torch))
-    if rc != 0:
-        raise RuntimeError(f"brdf_hip_model_eval_dev failed: {last_error()}")
+    _call("brdf_hip_model_eval_dev", angles.device, model, angles.data_ptr(), n, _dptr(pa), hx.data_ptr(), _STREAM)
     return hx
 
 
@@ -433,12 +422,8 @@ def cosines(vertices, faces, face_normals, leds, view_origin, *, surfels=None, r
     L = la.shape[0]
     va = _f64(view_origin, 3)
     out = torch.empty((S, 3, L), dtype=torch.float64, device=vertices.device)
-    with torch.cuda.device(vertices.device):
-        rc = lib.brdf_hip_cosines_dev(vertices.data_ptr(), faces.data_ptr(), face_normals.data_ptr(),
-                                      surfels.data_ptr() if surfels is not None else None, S, _dptr(la), L, _dptr(va), rv_mode,
-                                      out.data_ptr(), _stream_handle(torch))
-    if rc != 0:
-        raise RuntimeError(f"brdf_hip_cosines_dev failed: {last_error()}")
+    _call("brdf_hip_cosines_dev", vertices.device, vertices.data_ptr(), faces.data_ptr(), face_normals.data_ptr(),
+          surfels.data_ptr() if surfels is not None else None, S, _dptr(la), L, _dptr(va), rv_mode, out.data_ptr(), _STREAM)
     return out
 
 
@@ -461,76 +446,9 @@ def fit_capture_masked(model: int, images, pixel_map, vertices, faces, face_norm
     return (*out, surface_count)
 
 
-def fit_capture(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, rv_mode: int = 0,
-                p0=(0.5, 1.0, 1.0), lb=(0.0, 0.0, 0.0), ub=(100.0, 100.0, 100.0), itmax: int = 100, opts=None, brdf_surfaces=None,
-                validate: bool = True, want_stats: bool = False, surface_stats: FitStats | None = None, _mask=None):
-    """The pixel loop of CBRDFdata::CalcBRDFEquation (brdfdata.cpp:1188-1227) on the device.  images: CUDA uint8
-    [L,H,W,3] (BGR), pixel_map: CUDA int32 [H,W] (face index or -1), mesh as in cosines().  Returns (brdf_surfaces
-    CUDA float64 [nf,3,3] = {kd,ks,n} per face and channel, avg[3], number of pixels that carried a face).
-    want_stats=True (brdf_hip_fit_capture_stats_dev): a fourth value, FitStats with covar [nf,3,3,3], stats [nf,3,8],
-    rank [nf,3] of the fits that were stored (`surface_stats`: maps to write into; faces no pixel carries keep their
-    values, zeros by default)."""
-    import torch
-    images, pixel_map = images.contiguous(), pixel_map.contiguous()
-    vertices, faces, face_normals = vertices.contiguous(), faces.contiguous(), face_normals.contiguous()
-    _require(images.is_cuda and pixel_map.is_cuda and vertices.is_cuda and faces.is_cuda and face_normals.is_cuda, "bad argument: " 'images.is_cuda and pixel_map.is_cuda and vertices.is_cuda and faces.is_cuda and face_normals.is_cuda')
-    _require(images.dtype == torch.uint8 and pixel_map.dtype == torch.int32 and faces.dtype == torch.int32, "bad argument: " 'images.dtype == torch.uint8 and pixel_map.dtype == torch.int32 and faces.dtype == torch.int32')
-    _require(vertices.dtype == torch.float64 and face_normals.dtype == torch.float64, "bad argument: " 'vertices.dtype == torch.float64 and face_normals.dtype == torch.float64')
-    _require(images.dim() == 4 and images.shape[3] == 3 and tuple(pixel_map.shape) == tuple(images.shape[1:3]), "bad argument: " 'images.dim() == 4 and images.shape[3] == 3 and tuple(pixel_map.shape) == tuple(images.shape[1:3])')  # [L,H,W,3] BGR, [H,W]
-    _require(tuple(face_normals.shape) == (faces.shape[0], 3) and vertices.shape[-1] == 3, "bad argument: " 'tuple(face_normals.shape) == (faces.shape[0], 3) and vertices.shape[-1] == 3')
-    if validate:  # (-1 = no face under the pixel)
-        _check_indices(pixel_map, faces.shape[0], "pixel map names a face that does not exist", lower=-1)
-        _check_indices(faces, vertices.shape[0], "face index outside the vertex array")
-    L, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
-    nf = int(faces.shape[0])
-    if brdf_surfaces is None:
-        brdf_surfaces = torch.zeros((nf, 3, 3), dtype=torch.float64, device=images.device)
-    la = np.ascontiguousarray(leds, dtype=np.float64).reshape(-1, 3)
-    _require(la.shape[0] == L, "bad argument: " 'la.shape[0] == L')
-    va, pa, lba, uba = _f64(view_origin, 3), _f64(p0, 3), _f64(lb, 3), _f64(ub, 3)
-    oa = _f64(opts, 5) if opts is not None else None
-    avg = np.zeros(3)
-    npx = C.c_longlong(0)
-    args = (model, images.data_ptr(), L, H, W, pixel_map.data_ptr(), vertices.data_ptr(), faces.data_ptr(), face_normals.data_ptr(),
-            nf, _dptr(la), _dptr(va), rv_mode, _dptr(pa), _dptr(lba), _dptr(uba), itmax, _dptr(oa) if oa is not None else None,
-            brdf_surfaces.data_ptr(), _dptr(avg), C.byref(npx))
-    if not want_stats:
-        with torch.cuda.device(images.device):
-            rc = lib.brdf_hip_fit_capture_dev(*args, _stream_handle(torch))
-        if rc != 0:
-            raise RuntimeError(f"brdf_hip_fit_capture_dev failed: {last_error()}")
-        return brdf_surfaces, avg, npx.value
-    st = surface_stats
-    if st is None:
-        st = FitStats(torch.zeros((nf, 3, 3, 3), dtype=torch.float64, device=images.device),
-                      torch.zeros((nf, 3, 8), dtype=torch.float64, device=images.device),
-                      torch.zeros((nf, 3), dtype=torch.int32, device=images.device))
-    _require(tuple(st.covar.shape) == (nf, 3, 3, 3) and tuple(st.stats.shape) == (nf, 3, 8) and tuple(st.rank.shape) == (nf, 3),
-             "surface_stats: covar [nf,3,3,3], stats [nf,3,8], rank [nf,3]")
-    _require(st.covar.dtype == torch.float64 and st.stats.dtype == torch.float64 and st.rank.dtype == torch.int32,
-             "surface_stats: float64 covar and stats, int32 rank")
-    _require(st.covar.is_contiguous() and st.stats.is_contiguous() and st.rank.is_contiguous() and st.covar.is_cuda and st.stats.is_cuda
-             and st.rank.is_cuda, "surface_stats: contiguous CUDA tensors")
-    if _mask is not None:  # fit_capture_masked
-        with torch.cuda.device(images.device):
-            rc = lib.brdf_hip_fit_capture_masked_dev(*args, _stream_handle(torch), st.covar.data_ptr(), st.stats.data_ptr(), st.rank.data_ptr(),
-                                                     _mask[0], _mask[1], _mask[2], _mask[3].data_ptr())
-        if rc != 0:
-            raise RuntimeError(f"brdf_hip_fit_capture_masked_dev failed: {last_error()}")
-        return brdf_surfaces, avg, npx.value, st
-    with torch.cuda.device(images.device):
-        rc = lib.brdf_hip_fit_capture_stats_dev(*args, _stream_handle(torch), st.covar.data_ptr(), st.stats.data_ptr(), st.rank.data_ptr())
-    if rc != 0:
-        raise RuntimeError(f"brdf_hip_fit_capture_stats_dev failed: {last_error()}")
-    return brdf_surfaces, avg, npx.value, st
-
-
-def fit_capture_single(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, rv_mode: int = 0,
-                       p0=(0.0, 0.0, 0.0), lb=(0.0, 0.0, 0.0), ub=(100.0, 100.0, 100.0), itmax: int = 2000,
-                       opts=(1e-3, 1e-15, 1e-10, 1e-50, 1.0), validate: bool = True):
-    """CalcBRDFEquation_SingleBRDF (brdfdata.cpp:1138-1186) on the device: one {kd, ks, n} per colour channel for the
-    whole object.  Defaults are the reference's call-site values (brdfdata.cpp:1002, :1046-1056).  Returns
-    (single_brdf [3,3], info [3,10], faces used)."""
+def _capture_args(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, rv_mode, p0, lb, ub, itmax, opts, validate):
+    """What fit_capture and fit_capture_single share: the checks of the capture and the mesh, and the arguments the two entries have in
+    common, model ... opts.  Returns (those arguments, the tensors they point into, nf)."""
     import torch
     images, pixel_map = images.contiguous(), pixel_map.contiguous()
     vertices, faces, face_normals = vertices.contiguous(), faces.contiguous(), face_normals.contiguous()
@@ -547,15 +465,60 @@ def fit_capture_single(model: int, images, pixel_map, vertices, faces, face_norm
     la = np.ascontiguousarray(leds, dtype=np.float64).reshape(-1, 3)
     _require(la.shape[0] == L, "bad argument: " 'la.shape[0] == L')
     va, pa, lba, uba, oa = _f64(view_origin, 3), _f64(p0, 3), _f64(lb, 3), _f64(ub, 3), _f64(opts, 5)
+    args = (model, images.data_ptr(), L, H, W, pixel_map.data_ptr(), vertices.data_ptr(), faces.data_ptr(), face_normals.data_ptr(), nf,
+            _dptr(la), _dptr(va), rv_mode, _dptr(pa), _dptr(lba), _dptr(uba), itmax, _dptr(oa))
+    return args, (images, pixel_map, vertices, faces, face_normals), nf
+
+
+def fit_capture(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, rv_mode: int = 0,
+                p0=(0.5, 1.0, 1.0), lb=(0.0, 0.0, 0.0), ub=(100.0, 100.0, 100.0), itmax: int = 100, opts=None, brdf_surfaces=None,
+                validate: bool = True, want_stats: bool = False, surface_stats: FitStats | None = None, _mask=None):
+    """The pixel loop of CBRDFdata::CalcBRDFEquation (brdfdata.cpp:1188-1227) on the device.  images: CUDA uint8
+    [L,H,W,3] (BGR), pixel_map: CUDA int32 [H,W] (face index or -1), mesh as in cosines().  Returns (brdf_surfaces
+    CUDA float64 [nf,3,3] = {kd,ks,n} per face and channel, avg[3], number of pixels that carried a face).
+    want_stats=True (brdf_hip_fit_capture_stats_dev): a fourth value, FitStats with covar [nf,3,3,3], stats [nf,3,8],
+    rank [nf,3] of the fits that were stored (`surface_stats`: maps to write into; faces no pixel carries keep their
+    values, zeros by default)."""
+    import torch
+    args, keep, nf = _capture_args(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, rv_mode, p0, lb, ub, itmax, opts,
+                                   validate)
+    dev = keep[0].device
+    if brdf_surfaces is None:
+        brdf_surfaces = torch.zeros((nf, 3, 3), dtype=torch.float64, device=dev)
+    avg = np.zeros(3)
+    npx = C.c_longlong(0)
+    args += (brdf_surfaces.data_ptr(), _dptr(avg), C.byref(npx), _STREAM)
+    if not want_stats:
+        _call("brdf_hip_fit_capture_dev", dev, *args)
+        return brdf_surfaces, avg, npx.value
+    st = surface_stats
+    if st is None:
+        st = _zero_stats((nf, 3), dev)
+    _require(tuple(st.covar.shape) == (nf, 3, 3, 3) and tuple(st.stats.shape) == (nf, 3, 8) and tuple(st.rank.shape) == (nf, 3),
+             "surface_stats: covar [nf,3,3,3], stats [nf,3,8], rank [nf,3]")
+    _require(st.covar.dtype == torch.float64 and st.stats.dtype == torch.float64 and st.rank.dtype == torch.int32,
+             "surface_stats: float64 covar and stats, int32 rank")
+    _require(st.covar.is_contiguous() and st.stats.is_contiguous() and st.rank.is_contiguous() and st.covar.is_cuda and st.stats.is_cuda
+             and st.rank.is_cuda, "surface_stats: contiguous CUDA tensors")
+    args += (st.covar.data_ptr(), st.stats.data_ptr(), st.rank.data_ptr())
+    if _mask is not None:  # fit_capture_masked
+        _call("brdf_hip_fit_capture_masked_dev", dev, *args, _mask[0], _mask[1], _mask[2], _mask[3].data_ptr())
+    else:
+        _call("brdf_hip_fit_capture_stats_dev", dev, *args)
+    return brdf_surfaces, avg, npx.value, st
+
+
+def fit_capture_single(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, rv_mode: int = 0,
+                       p0=(0.0, 0.0, 0.0), lb=(0.0, 0.0, 0.0), ub=(100.0, 100.0, 100.0), itmax: int = 2000,
+                       opts=(1e-3, 1e-15, 1e-10, 1e-50, 1.0), validate: bool = True):
+    """CalcBRDFEquation_SingleBRDF (brdfdata.cpp:1138-1186) on the device: one {kd, ks, n} per colour channel for the
+    whole object.  Defaults are the reference's call-site values (brdfdata.cpp:1002, :1046-1056).  Returns
+    (single_brdf [3,3], info [3,10], faces used)."""
+    args, keep, _ = _capture_args(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, rv_mode, p0, lb, ub, itmax, opts,
+                                  validate)
     out, info = np.zeros(9), np.zeros(30)
     nfu = C.c_longlong(0)
-    with torch.cuda.device(images.device):
-        rc = lib.brdf_hip_fit_capture_single_dev(model, images.data_ptr(), L, H, W, pixel_map.data_ptr(), vertices.data_ptr(),
-                                                 faces.data_ptr(), face_normals.data_ptr(), nf, _dptr(la), _dptr(va), rv_mode,
-                                                 _dptr(pa), _dptr(lba), _dptr(uba), itmax, _dptr(oa), _dptr(out), _dptr(info),
-                                                 C.byref(nfu), _stream_handle(torch))
-    if rc != 0:
-        raise RuntimeError(f"brdf_hip_fit_capture_single_dev failed: {last_error()}")
+    _call("brdf_hip_fit_capture_single_dev", keep[0].device, *args, _dptr(out), _dptr(info), C.byref(nfu), _STREAM)
     return out.reshape(3, 3), info.reshape(3, 10), nfu.value
 
 

@@ -238,3 +238,49 @@ def test_switches_still_choose_the_class_0_kernel(gpu, monkeypatch):
             assert _same(np.ascontiguousarray(g[at]), w), (k, g[at], w)
     assert any((want[2] >= 0).any() for _, want in uni.values())  # (the comparison is not one of failures)
     print("the switched-off kernels' bytes differ from the default kernels':", not all(_same(a, b) for a, b in zip(default, got)))
+
+
+def test_host_pointer_entries_return_the_bytes_of_their_dev_entries(gpu):
+    """One fit of every count of COUNTS, Blinn-Phong dlevmar_bc_dif: brdf_hip_fit_batch_packed and brdf_hip_fit_stats_batch_packed
+    (host pointers: upload, the _dev entry, one wait, download) return the bytes of brdf_hip_fit_batch_packed_dev and
+    brdf_hip_fit_stats_batch_packed_dev, and brdf_hip_fit_batch_ragged (S = 5, stride 16) those of brdf_hip_fit_batch_ragged_dev."""
+    import ctypes as C
+    torch, brdf_amd, _ = gpu
+    from brdf_amd._lib import D, I, lib
+    model, method = 1, 1
+    fams = [f for f in FAMILIES if model in E.FAMILIES[f]]
+    fits, lb, ub = [], None, None
+    for j, k in enumerate(COUNTS):
+        a, xv, p, lb, ub = E.make(fams[j % len(fams)], model, max(k, 3), 0)
+        fits.append((np.ascontiguousarray(a[:, :k]), np.ascontiguousarray(xv[:k]), p))
+    S = len(fits)
+    packed = _pack(fits, list(range(S)))
+    want, _, _ = _packed(gpu, method, model, packed, lb, ub)
+    angles, x, offsets, p0 = (np.ascontiguousarray(a) for a in packed)
+    lba, uba, opts = (np.ascontiguousarray(v, dtype=np.float64) for v in (lb, ub, synth.OPTS))
+    p, info, ret = p0.copy(), np.zeros((S, 10)), np.zeros(S, dtype=np.int32)
+    failed = lib.brdf_hip_fit_batch_packed(method, model, angles.ctypes.data_as(D), x.ctypes.data_as(D), offsets.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                           S, p.ctypes.data_as(D), lba.ctypes.data_as(D), uba.ctypes.data_as(D), synth.ITMAX, opts.ctypes.data_as(D),
+                                           info.ctypes.data_as(D), ret.ctypes.data_as(I), 0)
+    assert failed == int((want[2] < 0).sum()) >= 2, brdf_amd.last_error()  # the number of fits with ret < 0 (the two refusals at least)
+    covar, stats, rank = np.zeros((S, 3, 3)), np.zeros((S, 8)), np.zeros(S, dtype=np.int32)
+    rc = lib.brdf_hip_fit_stats_batch_packed(method, model, angles.ctypes.data_as(D), x.ctypes.data_as(D), offsets.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                             S, p.ctypes.data_as(D), opts.ctypes.data_as(D), covar.ctypes.data_as(D), stats.ctypes.data_as(D),
+                                             rank.ctypes.data_as(I), 0)
+    assert rc == 0, brdf_amd.last_error()
+    for name, g, w in zip(NAMES, (p, info, ret, covar, stats, rank), want):
+        assert _same(g, w), ("packed", name, g, w)
+    assert np.any(want[2] >= 0) and np.any(want[5] == 3)  # (the comparison is not one of failures)
+    # the ragged fit pair
+    items = [(k, fams[j % len(fams)], 0) for j, k in enumerate((0, 2, 3, 7, 16))]
+    ra, rx, rp0, cnt, lb, ub = _ragged_arrays(model, 16, items)
+    dev = brdf_amd.fit_batch(method, model, _t(gpu, ra), _t(gpu, rx), _t(gpu, rp0), lb=lb, ub=ub, itmax=synth.ITMAX, opts=synth.OPTS, counts=_t(gpu, cnt))
+    torch.cuda.synchronize()
+    p, info, ret = rp0.copy(), np.zeros((5, 10)), np.zeros(5, dtype=np.int32)
+    failed = lib.brdf_hip_fit_batch_ragged(method, model, ra.ctypes.data_as(D), rx.ctypes.data_as(D), cnt.ctypes.data_as(I), 5, 16, p.ctypes.data_as(D),
+                                           lba.ctypes.data_as(D), uba.ctypes.data_as(D), synth.ITMAX, opts.ctypes.data_as(D), info.ctypes.data_as(D),
+                                           ret.ctypes.data_as(I))
+    assert failed == int((ret < 0).sum()) >= 2, brdf_amd.last_error()
+    for name, g, w in zip(NAMES, (p, info, ret), dev):
+        assert _same(g, w.cpu().numpy()), ("ragged", name, g, w)
+    assert np.any(ret >= 0)
