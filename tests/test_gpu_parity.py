@@ -1,9 +1,12 @@
 """GPU parity tests proper: the HIP path, called through the C ABI, against the CPU oracle on the same seeded
 inputs; against the committed reference fixtures; and, at BASELINE.json's full size, through size-independent
 properties.  Tolerances (SURVEY.md section 8d / BASELINE.json north_star): fitted parameters within 1e-5
-relative of the CPU levmar path, ||e||^2 within 1e-8 relative.  Trajectories (iteration / nfev counts) are NOT
-compared: the GPU sums in a tree, the reference sequentially, and accept/reject decisions near convergence are
-sensitive to the last bit."""
+relative of the CPU levmar path, ||e||^2 within 1e-8 relative.  Here a fit is compared at its fixed point only: the
+GPU sums in a tree, the reference sequentially, and accept/reject decisions near convergence are sensitive to the last
+bit, so the trajectories of full fits (iteration / nfev counts) differ.  Trajectories ARE compared where the reference
+itself determines them -- the first one, two and three iterations, fits that a loosened stop rule ends early, itmax = 0,
+opts = NULL and other tau / delta, in every regime: tests/test_gpu_passes.py holds ret, p and info[0..4] to each case's
+own tolerance (tests/pass_problems.py) and info[5..9] (iterations, reason, nfev, njev, nlss) exactly."""
 import ctypes as C
 import json
 import os
