@@ -695,6 +695,19 @@ int brdf_hip_fit_capture_masked_dev(int model, const unsigned char *d_images, in
                          d_surface_covar, d_surface_stats, d_surface_rank, &mask);
 }
 
+int brdf_hip_fit_capture_faces_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                   const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                   const double *view_origin, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
+                                   const double *opts, int v_min, int v_max, double cos_min, long long workspace_bytes,
+                                   double *d_brdf_surfaces, double *d_surface_info, int *d_surface_ret, double *d_surface_covar,
+                                   double *d_surface_stats, int *d_surface_rank, int *d_surface_count, int *d_face_pixels, double *avg,
+                                   long long *n_pixels, long long *n_faces, void *stream) {
+  const CaptureFacesArgs a = {model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin, rv_mode, p0, lb, ub,
+                              itmax, opts, v_min, v_max, cos_min, workspace_bytes, d_brdf_surfaces, d_surface_info, d_surface_ret, d_surface_covar,
+                              d_surface_stats, d_surface_rank, d_surface_count, d_face_pixels, avg, n_pixels, n_faces, static_cast<hipStream_t>(stream)};
+  return capture_faces_run(a);
+}
+
 int brdf_hip_fit_capture_single_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
                                     const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf,
                                     const double *leds, const double *view_origin, int rv_mode, const double *p0,

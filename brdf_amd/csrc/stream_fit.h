@@ -123,6 +123,37 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
                     double *d_surface_covar = nullptr, double *d_surface_stats = nullptr, int *d_surface_rank = nullptr,  // the optional statistics tail
                     const CaptureMask *mask = nullptr);  // brdf_hip_fit_capture_masked_dev: a validity rule, a ragged fit
 
+// brdf_hip_fit_capture_faces_dev (capture_faces.hip): one fit per (face, channel) over the valid samples of all the face's pixels,
+// through the packed batch.  The capture, the mesh and the fit's settings as capture_fit_run; the rule as CaptureMask.
+struct CaptureFacesArgs {
+  int model;
+  const unsigned char *d_images;
+  int L, H, W;
+  const int *d_pixel_map;
+  const double *d_vertices;
+  const int *d_faces;
+  const double *d_normals;
+  int nf;
+  const double *leds, *view;
+  int rv_mode;
+  const double *p0, *lb, *ub;
+  int itmax;
+  const double *opts;
+  int v_min, v_max;
+  double cos_min;
+  long long workspace_bytes;  // the packed calls'
+  double *d_brdf_surfaces;    // [nf][3][3]
+  double *d_surface_info;     // [nf][3][10] or null
+  int *d_surface_ret;         // [nf][3] or null
+  double *d_surface_covar, *d_surface_stats;  // [nf][3][9], [nf][3][kStatsSz] or null
+  int *d_surface_rank, *d_surface_count;      // [nf][3] or null
+  int *d_face_pixels;                         // [nf] or null
+  double *avg;                                // host [3] or null
+  long long *n_pixels, *n_faces;              // host or null
+  hipStream_t stream;
+};
+int capture_faces_run(const CaptureFacesArgs &a);  // refuses bad arguments before any HIP call
+
 // one model evaluation / analytic Jacobian over n samples (stream_fit.hip): d_hx [n], d_jac [n][3]
 int model_eval_run(int model, const double *d_angles, int n, const double *p, double *d_hx, hipStream_t stream);
 int model_jac_run(int model, const double *d_angles, int n, const double *p, double *d_jac, hipStream_t stream);

@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 
@@ -506,6 +507,100 @@ def fit_capture(model: int, images, pixel_map, vertices, faces, face_normals, le
     else:
         _call("brdf_hip_fit_capture_stats_dev", dev, *args)
     return brdf_surfaces, avg, npx.value, st
+
+
+class CaptureFaces(NamedTuple):
+    """What fit_capture_faces returns: the [nf,3] maps (CUDA tensors) and the call's host scalars."""
+    surfaces: object     # [nf,3,3] float64: {kd, ks, n} per face and channel
+    info: object         # [nf,3,10] float64: levmar's info[]
+    ret: object          # [nf,3] int32: iterations, or -1
+    stats: FitStats | None  # covar [nf,3,3,3], stats [nf,3,8], rank [nf,3]; None without want_stats
+    count: object        # [nf,3] int32: the samples of the fit
+    face_pixels: object  # [nf] int32: the pixels that carry the face (0 where none)
+    avg: np.ndarray      # [3]
+    n_pixels: int
+    n_faces: int
+
+
+def fit_capture_faces(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, v_min: int = 0, v_max: int = 255,
+                      cos_min: float = -2.0, rv_mode: int = 0, p0=(0.5, 1.0, 1.0), lb=(0.0, 0.0, 0.0), ub=(100.0, 100.0, 100.0),
+                      itmax: int = 100, opts=None, workspace_bytes: int = 0, want_stats: bool = True, validate: bool = True,
+                      out: CaptureFaces | None = None) -> CaptureFaces:
+    """The capture with ONE fit per (face, channel) over the samples of ALL the face's pixels (brdf_hip_fit_capture_faces_dev), where
+    fit_capture fits every pixel (n = L) and keeps the face's last one.  Arguments as fit_capture; the validity rule as
+    fit_capture_masked (the defaults switch it off).  Fit (face, channel)'s samples are the face's pixels in the reference's walk
+    (x outer, y inner), the lights inside a pixel, those the rule leaves -- group_capture_samples is this definition as code -- and its
+    result has the bytes fit_batch_packed / fit_stats_batch_packed give for that sample set: k - 3 degrees of freedom with k samples;
+    k < 3: ret -1, zero info, p0 in surfaces.  Faces no pixel carries keep what the maps held: zeros, or the values of `out`, an
+    earlier result (or one built by hand) whose tensors are written into.  A face of more than 4096 / L pixels runs through the
+    single-fit path, one such fit after the other.  Memory: 32 bytes per candidate sample (3 channels x pixels x L) at most, plus the
+    packed calls' workspace_bytes (0: 1 GiB).  The call waits for the stream."""
+    import torch
+    args, keep, nf = _capture_args(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, rv_mode, p0, lb, ub, itmax, opts,
+                                   validate)
+    dev = keep[0].device
+    if out is None:
+        def z(*shape, dtype=torch.float64):
+            return torch.zeros((nf, *shape), dtype=dtype, device=dev)
+        out = CaptureFaces(z(3, 3), z(3, 10), z(3, dtype=torch.int32), _zero_stats((nf, 3), dev) if want_stats else None, z(3, dtype=torch.int32),
+                           z(dtype=torch.int32), None, 0, 0)
+    _require(not want_stats or out.stats is not None, "out: want_stats needs out.stats")
+    st = out.stats if want_stats else None
+    maps = [(out.surfaces, (nf, 3, 3), torch.float64), (out.info, (nf, 3, 10), torch.float64), (out.ret, (nf, 3), torch.int32),
+            (out.count, (nf, 3), torch.int32), (out.face_pixels, (nf,), torch.int32)]
+    if st is not None:
+        maps += [(st.covar, (nf, 3, 3, 3), torch.float64), (st.stats, (nf, 3, 8), torch.float64), (st.rank, (nf, 3), torch.int32)]
+    for t, shape, dtype in maps:
+        _require(t.is_cuda and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(),
+                 f"out: contiguous CUDA {dtype} {list(shape)} tensors on the capture's device")
+    avg = np.zeros(3)
+    npx, nfc = C.c_longlong(0), C.c_longlong(0)
+    _call("brdf_hip_fit_capture_faces_dev", dev, *args, int(v_min), int(v_max), float(cos_min), int(workspace_bytes), out.surfaces.data_ptr(),
+          out.info.data_ptr(), out.ret.data_ptr(), None if st is None else st.covar.data_ptr(), None if st is None else st.stats.data_ptr(),
+          None if st is None else st.rank.data_ptr(), out.count.data_ptr(), out.face_pixels.data_ptr(), _dptr(avg), C.byref(npx), C.byref(nfc),
+          _STREAM)
+    return CaptureFaces(out.surfaces, out.info, out.ret, st, out.count, out.face_pixels, avg, npx.value, nfc.value)
+
+
+def group_capture_samples(images, pixel_map, face_angles, model: int, *, v_min: int = 0, v_max: int = 255, cos_min: float = -2.0):
+    """The host twin of fit_capture_faces' grouping (NumPy, no device): its definition as code.  images [L,H,W,3] uint8, pixel_map
+    [H,W] (entries outside [0, nf) are background), face_angles [nf,3,L] (the faces' cosine planes).  One fit per carried face and
+    channel, ordered by ascending face, then channel; its candidates are the face's pixels in the reference's walk (x outer, y inner),
+    within a pixel the lights 0 ... L-1; a candidate is a sample iff v_min <= image_i(H-1-y, x)[c] <= v_max and every plane the model
+    reads is > cos_min (a NaN is not).  Returns (angles [3 * total] float64, x [total], offsets [fits + 1] int64 -- the packed layout
+    fit_batch_packed reads --, fit_face [fits], fit_channel [fits], face_pixels [nf] int32)."""
+    images, pixel_map = np.asarray(images), np.asarray(pixel_map)
+    face_angles = np.ascontiguousarray(face_angles, dtype=np.float64)
+    _require(images.ndim == 4 and images.shape[3] == 3 and images.dtype == np.uint8 and pixel_map.shape == images.shape[1:3],
+             "images [L,H,W,3] uint8, pixel_map [H,W]")
+    L, H, W = images.shape[:3]
+    _require(face_angles.ndim == 3 and face_angles.shape[1:] == (3, L), "face_angles [nf,3,L]")
+    _require(model in (MODEL_PHONG, MODEL_BLINN_PHONG, MODEL_WARD), "unknown model")
+    nf = face_angles.shape[0]
+    walk = pixel_map.T.reshape(-1)  # the reference's walk: index x * H + y
+    carried = np.flatnonzero((walk > -1) & (walk < nf))
+    face = walk[carried].astype(np.int64)
+    face_pixels = np.bincount(face, minlength=nf).astype(np.int32)
+    order = np.argsort(face, kind="stable")  # by face, walk order kept inside a face
+    g, face = carried[order], face[order]
+    value = images[:, H - 1 - g % H, g // H, :].astype(np.int64)  # [L, pixels, 3]
+    reads = [True, model != MODEL_PHONG, model != MODEL_BLINN_PHONG]  # the planes the model reads
+    cos_ok = np.all([face_angles[face, k, :] > cos_min for k in range(3) if reads[k]], axis=0)  # [pixels, L]
+    angles, x, offsets, fit_face, fit_channel = [], [], [0], [], []
+    first = np.concatenate([[0], np.cumsum(face_pixels[face_pixels > 0])])
+    for r, f in enumerate(np.flatnonzero(face_pixels)):
+        rows = slice(first[r], first[r + 1])
+        for c in range(3):
+            v = value[:, rows, c].T  # [the face's pixels, L]: the candidates in their order
+            valid = cos_ok[rows] & (v >= v_min) & (v <= v_max)
+            angles.append(np.broadcast_to(face_angles[f][:, None, :], (3,) + v.shape)[:, valid].reshape(-1))
+            x.append(v[valid] / 255.0)
+            offsets.append(offsets[-1] + int(valid.sum()))
+            fit_face.append(f)
+            fit_channel.append(c)
+    cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0)  # noqa: E731
+    return (np.ascontiguousarray(cat(angles), dtype=np.float64), np.ascontiguousarray(cat(x), dtype=np.float64), np.array(offsets, dtype=np.int64),
+            np.array(fit_face, dtype=np.int32), np.array(fit_channel, dtype=np.int32), face_pixels)
 
 
 def fit_capture_single(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, rv_mode: int = 0,

@@ -314,7 +314,7 @@ int brdf_hip_fit_stats_batch_ragged(int method, int model, const double *angles,
  *               offsets that decrease and a fit of more than INT_MAX samples -- are refused before any HIP call.
  *   Host entries  upload the offsets[S] - offsets[0] samples the batch covers; brdf_hip_fit_batch_packed returns the number of fits
  *               that ended in LM_ERROR (refused ones included), as brdf_hip_fit_batch does.
- * Not covered: per-sample weights, dscl, a packed brdf_hip_fit_batch_multi, a capture entry that groups faces. */
+ * Not covered: per-sample weights, dscl, a packed brdf_hip_fit_batch_multi. */
 int brdf_hip_fit_batch_packed_dev(int method, int model, const double *d_angles, const double *d_x, const long long *d_offsets, int S,
                                   double *d_p, const double *lb, const double *ub, int itmax, const double *opts, double *d_info, int *d_ret,
                                   long long workspace_bytes, void *stream);
@@ -408,6 +408,52 @@ int brdf_hip_fit_capture_masked_dev(int model, const unsigned char *d_images, in
                                     double *avg, long long *n_pixels, void *stream, double *d_surface_covar,
                                     double *d_surface_stats, int *d_surface_rank, int v_min, int v_max, double cos_min,
                                     int *d_surface_count);
+
+/* The capture with ONE fit per (face, channel) over the samples of ALL the face's pixels, where the three entries above fit every
+ * pixel on its own (n = L) and keep the fit of the face's last pixel.  The capture becomes a packed batch on the device and the
+ * packed entries above fit it (BRDF_METHOD_BC_DIF); no fit or statistics kernel of its own.  Capture, mesh, leds, view_origin,
+ * rv_mode, p0 / lb / ub / itmax / opts as brdf_hip_fit_capture_dev.
+ *   Which fits     one fit for every face f, 0 <= f < nf, that at least one pixel carries, and every channel c (B, G, R).  Pixel-map
+ *                  entries outside [0, nf) are background, as in the entries above.
+ *   Candidates     of fit (f, c): the face's pixels in the reference's walk (x outer, y inner), within a pixel the lights
+ *                  i = 0 ... L-1.
+ *   Validity rule  a candidate takes part iff v_min <= image_i(H-1-y, x)[c] <= v_max AND every cosine plane the model reads is
+ *                  > cos_min -- the rule of brdf_hip_fit_capture_masked_dev, word for word (a NaN cosine is not valid);
+ *                  0, 255, cos_min < -1 switches it off.
+ *   Samples        the surviving candidates, in that order: the planes are the face's cosines (brdf_hip_cosines_dev, rv_mode as
+ *                  given -- all pixels of a face share them), the measurement is value / 255.0.
+ *   Result         fit (f, c) has the BYTES brdf_hip_fit_batch_packed_dev (BRDF_METHOD_BC_DIF) returns for that sample set -- by
+ *                  that entry's contract the bytes of brdf_hip_fit_batch_dev on the fit alone at n = k, its number of samples --
+ *                  from p0 with the call's box, itmax and opts.  The statistics maps hold the bytes of
+ *                  brdf_hip_fit_stats_batch_packed_dev at the fitted point: k - 3 degrees of freedom.
+ *   Too few        k < 3 is levmar's n < m refusal: ret = LM_ERROR, info all zeros, p0 in d_brdf_surfaces, the statistics the packed
+ *                  pass writes for such a count (rank 0); d_surface_count tells.
+ *   Maps           d_brdf_surfaces[nf][3][3] (required); d_surface_info[nf][3][10], d_surface_ret[nf][3], d_surface_covar[nf][3][9],
+ *                  d_surface_stats[nf][3][BRDF_STATS_SZ], d_surface_rank[nf][3], d_surface_count[nf][3] (the fit's k): DEVICE, each may
+ *                  be NULL.  Faces no pixel carries are left untouched in all of them.  d_face_pixels[nf] (DEVICE, may be NULL): the
+ *                  pixels that carry the face, written for EVERY face (0 where none).
+ *   Host scalars   avg[k] (or NULL): the sum over the (face, channel) rows this call wrote of d_brdf_surfaces[..][k], divided by
+ *                  nf * 3 -- a reduction in a fixed order: two calls give the same bytes; n_pixels: the pixels that carry a face;
+ *                  n_faces: the carried faces.
+ *   Big faces      a fit above 4096 samples -- a face of more than 4096 / L pixels under the rule switched off -- runs through the
+ *                  single-fit path, one after the other, as in the packed call.
+ *   Memory         32 bytes per candidate sample at most (3 channels x pixels x L candidates; the packed planes and measurements
+ *                  hold the valid ones), 24 bytes per carried pixel and the sort's scratch for the grouping, and the packed calls' own
+ *                  workspace_bytes (0: 1 GiB).
+ *   Refused before any HIP call: a NULL required pointer, L outside [1, 64], H, W or nf <= 0, 3 nf > INT_MAX, an unknown model,
+ *                  v_min > v_max, a NaN cos_min, workspace_bytes < 0, lb > ub.  Refused once the counts are known: a face with
+ *                  pixels x L > INT_MAX.  An allocation that fails returns LM_ERROR with the bytes asked for in the message.
+ *   Empty capture  no carried face: returns 0 with n_pixels = n_faces = 0 and a zero avg; nothing is written but d_face_pixels.
+ * Synchronises `stream` before returning.  Returns 0, or LM_ERROR with a message that names the entry in brdf_hip_last_error().
+ * Not covered: the count-weighted fit of per-light means (the same minimiser; it needs per-sample weights, which the library does not
+ * have) and a grouped brdf_hip_fit_capture_single_dev. */
+int brdf_hip_fit_capture_faces_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                   const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                   const double *view_origin, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
+                                   const double *opts, int v_min, int v_max, double cos_min, long long workspace_bytes,
+                                   double *d_brdf_surfaces, double *d_surface_info, int *d_surface_ret, double *d_surface_covar,
+                                   double *d_surface_stats, int *d_surface_rank, int *d_surface_count, int *d_face_pixels, double *avg,
+                                   long long *n_pixels, long long *n_faces, void *stream);
 
 /* Replaces CBRDFdata::CalcBRDFEquation_SingleBRDF (brdfdata.cpp:1138-1186) with SolveEquation_SingleBRDF (:992-1062): ONE
  * {kd, ks, n} per colour channel for the whole object, fitted with dlevmar_bc_dif to the L samples of every face the pixel
