@@ -432,7 +432,8 @@ def fit_capture_masked(model: int, images, pixel_map, vertices, faces, face_norm
                        cos_min: float = -2.0, surface_count=None, **kwargs):
     """fit_capture(want_stats=True) with a validity rule (brdf_hip_fit_capture_masked_dev): light i of a (pixel, channel) fit takes
     part iff v_min <= its 8-bit intensity <= v_max and every cosine plane the model reads is > cos_min; the fit is levmar on the
-    valid samples alone (a ragged fit).  The defaults switch both tests off: then every output is bit-identical to fit_capture's.
+    valid samples alone (a ragged fit).  The defaults switch both tests off: then every output is bit-identical to fit_capture's, except
+    that a NaN cosine is never a sample: on a face with NaN cosines the fit is refused (count 0) where fit_capture stops it with reason 7.
     Returns (brdf_surfaces, avg, pixels, FitStats, surface_count [nf,3] int32 CUDA: the sample count of each stored fit; a fit of
     fewer than 3 samples is refused and leaves p0 in brdf_surfaces).  Keyword arguments as fit_capture."""
     import torch

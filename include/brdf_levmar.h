@@ -399,7 +399,9 @@ int brdf_hip_fit_capture_stats_dev(int model, const unsigned char *d_images, int
  *   faces no pixel carries are left untouched.  A fit refused for count < 3 leaves p0 in d_brdf_surfaces, as any failed fit does:
  *   the count map is how the caller tells.
  * With both conditions off, d_brdf_surfaces, avg, n_pixels and the three statistics maps are bit-identical to
- * brdf_hip_fit_capture_stats_dev.  Returns LM_ERROR for v_min > v_max as for the other bad arguments, before any HIP call.
+ * brdf_hip_fit_capture_stats_dev wherever the cosines are numbers.  A NaN cosine is never a sample, also with the rule switched off;
+ * on such a face (a degenerate triangle with a NaN normal) the rule-off call refuses the fit -- count 0, p0 in d_brdf_surfaces,
+ * sumsq = R2 = 0 -- where the unmasked capture stops it with reason 7: p0 as well, but a NaN sumsq and R2.  Returns LM_ERROR for v_min > v_max as for the other bad arguments, before any HIP call.
  * Not covered: brdf_hip_fit_capture_single_dev (masking there changes one big fit's n) and the multi-GPU batch. */
 int brdf_hip_fit_capture_masked_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
                                     const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf,
@@ -418,8 +420,9 @@ int brdf_hip_fit_capture_masked_dev(int model, const unsigned char *d_images, in
  *   Candidates     of fit (f, c): the face's pixels in the reference's walk (x outer, y inner), within a pixel the lights
  *                  i = 0 ... L-1.
  *   Validity rule  a candidate takes part iff v_min <= image_i(H-1-y, x)[c] <= v_max AND every cosine plane the model reads is
- *                  > cos_min -- the rule of brdf_hip_fit_capture_masked_dev, word for word (a NaN cosine is not valid);
- *                  0, 255, cos_min < -1 switches it off.
+ *                  > cos_min -- the rule of brdf_hip_fit_capture_masked_dev, word for word; 0, 255, cos_min < -1 switches it off.
+ *                  A NaN cosine is never a sample, also with the rule switched off; on such a face the rule-off call refuses the
+ *                  fit (count 0) where the unmasked capture stops it with reason 7.
  *   Samples        the surviving candidates, in that order: the planes are the face's cosines (brdf_hip_cosines_dev, rv_mode as
  *                  given -- all pixels of a face share them), the measurement is value / 255.0.
  *   Result         fit (f, c) has the BYTES brdf_hip_fit_batch_packed_dev (BRDF_METHOD_BC_DIF) returns for that sample set -- by

@@ -233,3 +233,106 @@ def test_device_single_brdf_capture_against_oracle(gpu):
     for ch in range(3):
         assert L.rel_err(got[ch], want[ch]) <= 1e-5, (ch, got[ch], want[ch])
         assert abs(info[ch, 1] - info_ref[ch, 1]) <= 1e-8 * info_ref[ch, 1]
+
+
+# ---- both cosines kernels at the light counts, surfel counts and centroids the tests above do not reach ---------------------
+_BIG_MESH = []
+
+
+def _big_mesh():
+    """the mesh of test_device_cosines_bit_exact, built once"""
+    if not _BIG_MESH:
+        _BIG_MESH.append(make_mesh(nv=4000, nf=30011, seed=11))
+    return _BIG_MESH[0]
+
+
+def _device_cosines(gpu, mesh, leds, rv_mode, surfels=None):
+    torch, brdf_amd, dev = gpu
+    vertices, faces, nrm, view = mesh
+    tv, tf, tn = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (vertices, faces, nrm))
+    ts = None if surfels is None else torch.from_numpy(surfels).to(dev)
+    return brdf_amd.cosines(tv, tf, tn, leds, view, surfels=ts, rv_mode=rv_mode).cpu().numpy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rv_mode", [0, 1])
+def test_device_cosines_one_lane_per_light_kernel_at_16_lights(gpu, monkeypatch, rv_mode):
+    """BRDF_HIP_COSINES_ROWS=0: cosines_kernel where the rows kernel runs by default -- the oracle's bits, and so the default's"""
+    mesh = _big_mesh()
+    vertices, faces, nrm, view = mesh
+    leds = L.led_table()
+    surfels = np.random.default_rng(5).integers(0, faces.shape[0], size=1001).astype(np.int32)
+    want = L.cosines(vertices, faces, nrm, leds, view, rv_mode=rv_mode)
+    want_s = L.cosines(vertices, faces, nrm, leds, view, surfels=surfels, rv_mode=rv_mode)
+    rows, rows_s = _device_cosines(gpu, mesh, leds, rv_mode), _device_cosines(gpu, mesh, leds, rv_mode, surfels)
+    monkeypatch.setenv("BRDF_HIP_COSINES_ROWS", "0")
+    lanes, lanes_s = _device_cosines(gpu, mesh, leds, rv_mode), _device_cosines(gpu, mesh, leds, rv_mode, surfels)
+    assert np.array_equal(lanes, want) and np.array_equal(lanes_s, want_s)
+    assert lanes.tobytes() == rows.tobytes() and lanes_s.tobytes() == rows_s.tobytes()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lights", [1, 64])
+@pytest.mark.parametrize("rv_mode", [0, 1])
+def test_device_cosines_at_1_and_64_lights(gpu, rv_mode, lights):
+    from tests.capture_problems import leds_for
+    mesh = _big_mesh()
+    vertices, faces, nrm, view = mesh
+    leds = leds_for(lights)
+    got = _device_cosines(gpu, mesh, leds, rv_mode)
+    assert got.shape == (faces.shape[0], 3, lights) and np.array_equal(got, L.cosines(vertices, faces, nrm, leds, view, rv_mode=rv_mode))
+    surfels = np.random.default_rng(6).integers(0, faces.shape[0], size=1001).astype(np.int32)
+    assert np.array_equal(_device_cosines(gpu, mesh, leds, rv_mode, surfels), L.cosines(vertices, faces, nrm, leds, view, surfels=surfels, rv_mode=rv_mode))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rows", ["1", "0"])
+def test_device_cosines_past_one_trip_of_the_grid(gpu, monkeypatch, rows):
+    """262,144 + 53 surfels at 16 lights: 16,384 workgroups of 16 surfels and a second trip of the grid-stride loop, in both kernels"""
+    mesh = _big_mesh()
+    vertices, faces, nrm, view = mesh
+    leds = L.led_table()
+    surfels = np.random.default_rng(7).integers(0, faces.shape[0], size=262144 + 53).astype(np.int32)
+    want = L.cosines(vertices, faces, nrm, leds, view, surfels=surfels, rv_mode=1)
+    monkeypatch.setenv("BRDF_HIP_COSINES_ROWS", rows)
+    got = _device_cosines(gpu, mesh, leds, 1, surfels)
+    assert np.array_equal(got, want)
+    assert np.array_equal(got[262144:], want[262144:]) and np.array_equal(got[-53:], L.cosines(vertices, faces, nrm, leds, view, surfels=surfels[-53:], rv_mode=1))
+
+
+def zero_sum_mesh():
+    """faces whose vertex sums are exactly 0.0 in one, two and three axes (small integers: every partial sum is exact), and one
+    ordinary face; the centroid's zero components take the `t == 0` branch in front of the kernels' division by three"""
+    vertices = np.array([[1.0, 2.0, 3.0], [2.0, -5.0, 1.0], [-3.0, 3.0, -4.0],     # face 0: sums (0, 0, 0)
+                         [4.0, 1.0, 7.0], [-1.0, -3.0, 2.0], [-3.0, 2.0, 5.0],     # face 1: sums (0, 0, 14)
+                         [6.0, -2.0, 1.0], [-2.0, 5.0, 9.0], [-4.0, 8.0, 3.0],     # face 2: sums (0, 11, 13)
+                         [3.0, 7.0, -6.0], [5.0, -7.0, 2.0], [9.0, 4.0, 4.0],      # face 3: sums (17, 4, 0)
+                         [8.0, 1.0, 2.0], [1.0, 6.0, -3.0], [2.0, 2.0, 5.0]])      # face 4: sums (11, 9, 4)
+    faces = np.arange(15, dtype=np.int32).reshape(5, 3)
+    nrm = np.cross(vertices[faces[:, 1]] - vertices[faces[:, 0]], vertices[faces[:, 2]] - vertices[faces[:, 0]])
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    return vertices, faces, nrm, np.array([310.0, -75.0, 700.0])
+
+
+def test_zero_sum_mesh_has_zero_centroid_components():
+    vertices, faces, nrm, _ = zero_sum_mesh()
+    sums = vertices[faces].sum(axis=1)
+    assert [int((s == 0.0).sum()) for s in sums] == [3, 2, 1, 1, 0] and np.all(np.isfinite(nrm))
+    for rv_mode in (0, 1):  # the oracle and the numpy restatement agree there too
+        got = L.cosines(vertices, faces, nrm, L.led_table(), np.array([310.0, -75.0, 700.0]), rv_mode=rv_mode)
+        assert np.max(np.abs(got - numpy_cosines(vertices, faces, nrm, L.led_table(), np.array([310.0, -75.0, 700.0]), rv_mode))) <= 4e-15
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rv_mode", [0, 1])
+def test_device_cosines_with_zero_centroid_components(gpu, monkeypatch, rv_mode):
+    mesh = zero_sum_mesh()
+    vertices, faces, nrm, view = mesh
+    surfels = np.array([0, 4, 1, 0, 2, 3, 3, 0], dtype=np.int32)
+    for lights in (16, 5):
+        leds = L.led_table()[:lights]
+        for rows in ("1", "0"):
+            monkeypatch.setenv("BRDF_HIP_COSINES_ROWS", rows)
+            assert np.array_equal(_device_cosines(gpu, mesh, leds, rv_mode), L.cosines(vertices, faces, nrm, leds, view, rv_mode=rv_mode), equal_nan=True)
+            assert np.array_equal(_device_cosines(gpu, mesh, leds, rv_mode, surfels),
+                                  L.cosines(vertices, faces, nrm, leds, view, surfels=surfels, rv_mode=rv_mode), equal_nan=True)
