@@ -67,6 +67,12 @@ ABI = {
     "brdf_hip_fit_stats_batch_ragged_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, D,
                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "brdf_hip_fit_stats_batch_ragged": (C.c_int, [C.c_int, C.c_int, D, D, I, C.c_int, C.c_int, D, D, D, D, I]),
+    "brdf_hip_fit_batch_weighted_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, D,
+                                                  D, C.c_int, D, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "brdf_hip_fit_batch_weighted": (C.c_int, [C.c_int, C.c_int, D, D, D, I, C.c_int, C.c_int, D, D, D, C.c_int, D, D, I]),
+    "brdf_hip_fit_stats_batch_weighted_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                        C.c_void_p, D, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "brdf_hip_fit_stats_batch_weighted": (C.c_int, [C.c_int, C.c_int, D, D, D, I, C.c_int, C.c_int, D, D, D, I, D, D, I]),
     "brdf_hip_fit_batch_packed_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, D, D, C.c_int, D,
                                                 C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "brdf_hip_fit_batch_packed": (C.c_int, [C.c_int, C.c_int, D, D, C.POINTER(C.c_longlong), C.c_int, D, D, D, C.c_int, D, D, I, C.c_longlong]),
@@ -93,6 +99,10 @@ ABI = {
     "brdf_hip_fit_capture_faces_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, C.c_int, C.c_int, C.c_double,
                                                  C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, D, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p]),
+    "brdf_hip_fit_capture_means_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, C.c_int, C.c_int, C.c_double,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, D, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p]),
     "brdf_hip_fit_capture_single_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, D, D,

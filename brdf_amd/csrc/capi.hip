@@ -19,6 +19,7 @@
 #include "fit_host.h"
 #include "fit_stats.h"
 #include "packed_fit.h"
+#include "weighted_fit.h"
 
 using namespace brdf;
 
@@ -558,6 +559,66 @@ int brdf_hip_fit_stats_batch_ragged(int method, int model, const double *angles,
   return fit_stats_host("brdf_hip_fit_stats_batch_ragged", method, model, angles, x, counts, S, n, p, opts, covar, stats, rank);
 }
 
+/* ---- per-sample weights, n <= 16 (weighted_fit.hip; the statistics: fit_stats.hip) --------------------------------------------- */
+int brdf_hip_fit_batch_weighted_dev(int method, int model, const double *d_angles, const double *d_x, const double *d_w, const int *d_counts,
+                                    int S, int n, double *d_p, const double *lb, const double *ub, int itmax, const double *opts,
+                                    double *d_info, int *d_ret, void *stream) {
+  const WeightedFitArgs a = {{method, model, d_angles, d_x, S, n, d_p, lb, ub, itmax, opts, d_info, d_ret, static_cast<hipStream_t>(stream), d_counts},
+                             d_w};
+  return weighted_fit_enqueue(a, "brdf_hip_fit_batch_weighted_dev");
+}
+
+int brdf_hip_fit_batch_weighted(int method, int model, const double *angles, const double *x, const double *w, const int *counts, int S, int n,
+                                double *p, const double *lb, const double *ub, int itmax, const double *opts, double *info, int *ret) {
+  const char *who = "brdf_hip_fit_batch_weighted";
+  WeightedFitArgs a = {{method, model, angles, x, S, n, p, lb, ub, itmax, opts, info, ret, nullptr, counts}, w};
+  if (weighted_fit_check(a, who) != 0) return LM_ERROR;
+  std::vector<int> own_ret(ret ? 0 : S);
+  if (!ret) ret = own_ret.data();
+  const size_t sn = (size_t)S * n;
+  HostCall h(who);
+  a.fit.d_angles = h.in(angles, 3 * sn);
+  a.fit.d_x = h.in(x, sn);
+  a.d_w = h.in(w, sn);
+  a.fit.d_counts = h.in(counts, S);
+  a.fit.d_p = h.inout(p, 3 * (size_t)S);
+  a.fit.d_info = h.out(info, 10 * (size_t)S);
+  a.fit.d_ret = h.out(ret, S);
+  if (h.failed() || weighted_fit_enqueue(a, who) != 0 || h.finish() != 0) return LM_ERROR;
+  return count_failed(ret, S);
+}
+
+int brdf_hip_fit_stats_batch_weighted_dev(int method, int model, const double *d_angles, const double *d_x, const double *d_w,
+                                          const int *d_counts, int S, int n, const double *d_p, const double *opts, const double *d_extra_ss,
+                                          const int *d_nobs, double *d_covar, double *d_stats, int *d_rank, void *stream) {
+  const WeightedStatsArgs a = {{method, model, d_angles, d_x, S, n, d_p, opts, d_covar, d_stats, d_rank, nullptr, 0, static_cast<hipStream_t>(stream),
+                                d_counts},
+                               d_w, d_extra_ss, d_nobs};
+  return weighted_stats_enqueue(a, "brdf_hip_fit_stats_batch_weighted_dev");
+}
+
+int brdf_hip_fit_stats_batch_weighted(int method, int model, const double *angles, const double *x, const double *w, const int *counts, int S,
+                                      int n, const double *p, const double *opts, const double *extra_ss, const int *nobs, double *covar,
+                                      double *stats, int *rank) {
+  const char *who = "brdf_hip_fit_stats_batch_weighted";
+  WeightedStatsArgs a = {{method, model, angles, x, S, n, p, opts, covar, stats, rank, nullptr, 0, nullptr, counts}, w, extra_ss, nobs};
+  if (weighted_stats_check(a, who) != 0) return LM_ERROR;
+  const size_t sn = (size_t)S * n;
+  HostCall h(who);
+  a.stats.d_angles = h.in(angles, 3 * sn);
+  a.stats.d_x = h.in(x, sn);
+  a.d_w = h.in(w, sn);
+  a.stats.d_counts = h.in(counts, S);
+  a.stats.d_p = h.in(p, 3 * (size_t)S);
+  a.d_extra_ss = h.in(extra_ss, S);
+  a.d_nobs = h.in(nobs, S);
+  a.stats.d_covar = h.out(covar, 9 * (size_t)S);
+  a.stats.d_stats = h.out(stats, BRDF_STATS_SZ * (size_t)S);
+  a.stats.d_rank = h.out(rank, S);
+  if (h.failed() || weighted_stats_enqueue(a, who) != 0 || h.finish() != 0) return LM_ERROR;
+  return 0;
+}
+
 /* ---- packed batches (packed_fit.hip) ---------------------------------------------------------------------------------------- */
 int brdf_hip_fit_batch_packed_dev(int method, int model, const double *d_angles, const double *d_x, const long long *d_offsets, int S,
                                   double *d_p, const double *lb, const double *ub, int itmax, const double *opts, double *d_info, int *d_ret,
@@ -706,6 +767,19 @@ int brdf_hip_fit_capture_faces_dev(int model, const unsigned char *d_images, int
                               itmax, opts, v_min, v_max, cos_min, workspace_bytes, d_brdf_surfaces, d_surface_info, d_surface_ret, d_surface_covar,
                               d_surface_stats, d_surface_rank, d_surface_count, d_face_pixels, avg, n_pixels, n_faces, static_cast<hipStream_t>(stream)};
   return capture_faces_run(a);
+}
+
+int brdf_hip_fit_capture_means_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                   const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                   const double *view_origin, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
+                                   const double *opts, int v_min, int v_max, double cos_min, double *d_brdf_surfaces, double *d_surface_info,
+                                   int *d_surface_ret, double *d_surface_covar, double *d_surface_stats, int *d_surface_rank, int *d_surface_count,
+                                   int *d_surface_lights, int *d_face_pixels, double *avg, long long *n_pixels, long long *n_faces, void *stream) {
+  const CaptureMeansArgs a = {{model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin, rv_mode, p0, lb, ub,
+                               itmax, opts, v_min, v_max, cos_min, 0, d_brdf_surfaces, d_surface_info, d_surface_ret, d_surface_covar,
+                               d_surface_stats, d_surface_rank, d_surface_count, d_face_pixels, avg, n_pixels, n_faces, static_cast<hipStream_t>(stream)},
+                              d_surface_lights};
+  return capture_means_run(a);
 }
 
 int brdf_hip_fit_capture_single_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,

@@ -2,6 +2,7 @@
 // the capture loop of capture_fit.hip fits every pixel and keeps the face's last one.  No fit or statistics kernel of its own: the
 // capture becomes a packed batch (packed_fit.h) on the device, the packed calls fit it, a scatter fills the [nf][3] maps.
 //
+// (compact, group and cosines are capture_group.h's, shared with capture_means.hip)
 //   compact   the pixels that carry a face, in the reference's x-major walk (the two-pass compaction of capture_fit.hip), and the
 //             number of pixels of every face (integer adds: their order cannot show)
 //   group     a stable radix sort of the compacted pixels by face (rocPRIM; walk order kept inside a face); one scan over the faces
@@ -16,15 +17,8 @@
 //   scatter   rows (face, channel) in ascending order: p, info, ret, the statistics, the counts; block sums of p in a fixed order
 //
 // The three candidate passes evaluate the same rule on the same bytes, so the places of pass 2 and 3 are the counts of pass 1.
-#include <climits>
-#include <cstring>  // (in front of rocPRIM, whose headers use memset without it)
-#include <vector>
-
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "../../include/brdf_levmar.h"
-#include "capture_compact.h"
-#include "fit_host.h"
+#include "capture_group.h"
 #include "fit_stats.h"
 #include "packed_fit.h"
 
@@ -33,79 +27,6 @@ namespace brdf {
 namespace {
 
 constexpr const char *kWho = "brdf_hip_fit_capture_faces_dev";
-constexpr int kWaves = kCT / kWave;
-
-// pass 2 of the pixel compaction, as capture_fit.hip's compact_kernel; instead of a face's last pixel it counts the face's pixels
-__global__ __launch_bounds__(kCT) void compact_faces_kernel(const int *pm, int H, int W, int nf, const long long *block_offset,
-                                                            long long *pixel_of, unsigned *face_of_surfel, int *face_pixels) {
-  __shared__ int wave_cnt[kWaves];
-  const long long g = (long long)blockIdx.x * kCT + threadIdx.x;
-  const int f = (g < (long long)H * W) ? face_of(pm, H, W, g) : -1;
-  const bool valid = f > -1 && f < nf;
-  const unsigned long long m = __ballot(valid);
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  if (lane == 0) wave_cnt[wave] = __popcll(m);
-  __syncthreads();
-  if (!valid) return;
-  long long s = block_offset[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wave; ++w) s += wave_cnt[w];
-  pixel_of[s] = g;
-  face_of_surfel[s] = (unsigned)f;
-  atomicAdd(face_pixels + f, 1);
-}
-
-// One workgroup over the faces: the carried faces in ascending order (face_list[F]), where each one's pixels start among the sorted
-// pixels (face_first[F + 1]) and its rank (rank_of_face[nf], -1 for a face no pixel carries); head = {F, the largest pixel count}.
-__global__ __launch_bounds__(kCT) void face_scan_kernel(const int *__restrict__ face_pixels, int nf, int *__restrict__ face_list,
-                                                        long long *__restrict__ face_first, int *__restrict__ rank_of_face,
-                                                        long long *__restrict__ head) {
-  __shared__ long long part_px[kCT];
-  __shared__ int part_f[kCT], part_mx[kCT];
-  const int t = threadIdx.x;
-  const long long per = ((long long)nf + kCT - 1) / kCT;
-  const long long b0 = t * per < nf ? t * per : nf, b1 = b0 + per < nf ? b0 + per : nf;
-  long long px = 0;
-  int fc = 0, mx = 0;
-  for (long long f = b0; f < b1; ++f) {
-    const int k = face_pixels[f];
-    px += k;
-    fc += k > 0;
-    mx = k > mx ? k : mx;
-  }
-  part_px[t] = px;
-  part_f[t] = fc;
-  part_mx[t] = mx;
-  __syncthreads();
-  if (t == 0) {
-    long long run_px = 0;
-    int run_f = 0, all_mx = 0;
-    for (int i = 0; i < kCT; ++i) {
-      const long long v = part_px[i];
-      const int c = part_f[i];
-      part_px[i] = run_px;
-      part_f[i] = run_f;
-      run_px += v;
-      run_f += c;
-      all_mx = part_mx[i] > all_mx ? part_mx[i] : all_mx;
-    }
-    head[0] = run_f;
-    head[1] = all_mx;
-    face_first[run_f] = run_px;
-  }
-  __syncthreads();
-  px = part_px[t];
-  fc = part_f[t];
-  for (long long f = b0; f < b1; ++f) {
-    const int k = face_pixels[f];
-    rank_of_face[f] = k > 0 ? fc : -1;
-    if (k > 0) {
-      face_list[fc] = (int)f;
-      face_first[fc] = px;
-      ++fc;
-      px += k;
-    }
-  }
-}
 
 // ---- count and pack ------------------------------------------------------------------------------------------------------------
 struct PackCtx {
@@ -280,8 +201,6 @@ __global__ __launch_bounds__(kCT) void face_scatter_kernel(FaceScatterCtx c) {
   if (threadIdx.x < 3) c.block_sums[(size_t)blockIdx.x * 3 + threadIdx.x] = red[threadIdx.x][0];
 }
 
-using DevBuf = DeviceBlock<char>;  // scoped: bytes
-
 #define FACES_OK(call)                                                        \
   do {                                                                        \
     hipError_t e_ = (call);                                                   \
@@ -292,36 +211,15 @@ using DevBuf = DeviceBlock<char>;  // scoped: bytes
   } while (0)
 
 // `bytes` of device memory for `what`; a failure names the bytes asked for
-bool take(DevBuf &b, size_t bytes, const char *what) {
-  const hipError_t e = b.ensure(bytes);
-  if (e == hipSuccess) return true;
-  (void)hipGetLastError();
-  set_error("%s(): cannot allocate %zu bytes for %s: %s", kWho, bytes, what, hipGetErrorString(e));
-  return false;
-}
+bool take(DevBuf &b, size_t bytes, const char *what) { return take(b, bytes, what, kWho); }
 
 // what the entry refuses before any HIP call
 int capture_faces_check(const CaptureFacesArgs &a) {
-  if (!a.d_images || !a.d_pixel_map || !a.d_vertices || !a.d_faces || !a.d_normals || !a.leds || !a.view || !a.p0 || !a.d_brdf_surfaces) {
-    set_error("%s(): null images, pixel map, mesh, leds, view origin, p0 or brdf_surfaces", kWho);
-    return kLmError;
-  }
-  if (a.L < 1 || a.L > 64 || a.H <= 0 || a.W <= 0 || a.nf <= 0 || a.nf > INT_MAX / 3) {
-    set_error("%s(): L = %d, H = %d, W = %d, nf = %d: need 1 <= L <= 64, H, W, nf > 0 and 3 nf <= INT_MAX", kWho, a.L, a.H, a.W, a.nf);
-    return kLmError;
-  }
-  MethodSpec ms;
-  if (!known_model_method(a.model, BRDF_METHOD_BC_DIF, &ms, kWho)) return kLmError;
-  if (a.v_min > a.v_max || a.cos_min != a.cos_min) {
-    set_error("%s(): bad validity rule (v_min %d > v_max %d, or cos_min not a number)", kWho, a.v_min, a.v_max);
-    return kLmError;
-  }
   if (a.workspace_bytes < 0) {
     set_error("%s(): workspace_bytes = %lld: need workspace_bytes >= 0", kWho, a.workspace_bytes);
     return kLmError;
   }
-  if (box_refused(ms, a.lb, a.ub, kWho)) return kLmError;
-  return 0;
+  return capture_args_check(kWho, a, 64, "");
 }
 
 }  // namespace
@@ -335,85 +233,13 @@ int capture_faces_run(const CaptureFacesArgs &a) {
   if (a.n_pixels) *a.n_pixels = 0;
   if (a.n_faces) *a.n_faces = 0;
 
-  // ---- compact: the pixels that carry a face, in walk order ----
-  const long long npx = (long long)H * W;
-  if ((npx + kCT - 1) / kCT > INT_MAX) {
-    set_error("%s(): H x W = %lld pixels are more than one launch walks", kWho, npx);
-    return kLmError;
-  }
-  const int nb = (int)((npx + kCT - 1) / kCT);
-  DevBuf counts, block_off, face_pixels;
-  if (!take(counts, sizeof(int) * nb, "the pixel blocks' counts") || !take(block_off, sizeof(long long) * nb, "the pixel blocks' offsets") ||
-      !take(face_pixels, sizeof(int) * (size_t)nf, "the faces' pixel counts"))
-    return kLmError;
-  FACES_OK(hipMemsetAsync(face_pixels.ptr, 0, sizeof(int) * (size_t)nf, stream));
-  hipLaunchKernelGGL(count_kernel, dim3(nb), dim3(kCT), 0, stream, a.d_pixel_map, H, W, nf, counts.as<int>());
-  FACES_OK(hipGetLastError());
-  std::vector<int> h_counts(nb);
-  FACES_OK(hipMemcpyAsync(h_counts.data(), counts.ptr, sizeof(int) * nb, hipMemcpyDeviceToHost, stream));
-  FACES_OK(hipStreamSynchronize(stream));
-  std::vector<long long> h_off(nb);
-  long long S = 0;
-  for (int b = 0; b < nb; ++b) {
-    h_off[b] = S;
-    S += h_counts[b];
-  }
-  if (S == 0) {  // an empty capture: nothing is written but the pixel counts
-    if (a.d_face_pixels) FACES_OK(hipMemcpyAsync(a.d_face_pixels, face_pixels.ptr, sizeof(int) * (size_t)nf, hipMemcpyDeviceToDevice, stream));
-    FACES_OK(hipStreamSynchronize(stream));
-    return 0;
-  }
-  const long long T = S * L;  // candidates of one channel
-  if (S > INT_MAX || (T + kCT - 1) / kCT > INT_MAX) {
-    set_error("%s(): %lld pixels carry a face, %lld candidates per channel: more than one launch walks", kWho, S, T);
-    return kLmError;
-  }
-  FACES_OK(hipMemcpyAsync(block_off.ptr, h_off.data(), sizeof(long long) * nb, hipMemcpyHostToDevice, stream));
-  DevBuf pixel_of, face_s, pixel_sorted, face_sorted, sort_tmp;
-  if (!take(pixel_of, sizeof(long long) * S, "the carried pixels") || !take(face_s, sizeof(unsigned) * S, "the carried pixels' faces") ||
-      !take(pixel_sorted, sizeof(long long) * S, "the grouped pixels") || !take(face_sorted, sizeof(unsigned) * S, "the grouped pixels' faces"))
-    return kLmError;
-  hipLaunchKernelGGL(compact_faces_kernel, dim3(nb), dim3(kCT), 0, stream, a.d_pixel_map, H, W, nf, block_off.as<long long>(),
-                     pixel_of.as<long long>(), face_s.as<unsigned>(), face_pixels.as<int>());
-  FACES_OK(hipGetLastError());
-
-  // ---- group: a stable sort by face keeps the walk order inside a face; the carried faces and where their pixels start ----
-  unsigned end_bit = 1;
-  while ((1LL << end_bit) < nf) ++end_bit;
-  size_t tmp_bytes = 0;
-  FACES_OK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, face_s.as<unsigned>(), face_sorted.as<unsigned>(), pixel_of.as<long long>(),
-                                     pixel_sorted.as<long long>(), (size_t)S, 0u, end_bit, stream));
-  if (!take(sort_tmp, tmp_bytes, "the sort of the pixels by face")) return kLmError;
-  FACES_OK(rocprim::radix_sort_pairs(sort_tmp.ptr, tmp_bytes, face_s.as<unsigned>(), face_sorted.as<unsigned>(), pixel_of.as<long long>(),
-                                     pixel_sorted.as<long long>(), (size_t)S, 0u, end_bit, stream));
-  DevBuf face_list, face_first, rank_of_face, head;
-  if (!take(face_list, sizeof(int) * (size_t)nf, "the carried faces") || !take(face_first, sizeof(long long) * ((size_t)nf + 1), "the faces' first pixels") ||
-      !take(rank_of_face, sizeof(int) * (size_t)nf, "the faces' ranks") || !take(head, sizeof(long long) * 3, "the counts the host reads"))
-    return kLmError;
-  hipLaunchKernelGGL(face_scan_kernel, dim3(1), dim3(kCT), 0, stream, face_pixels.as<int>(), nf, face_list.as<int>(), face_first.as<long long>(),
-                     rank_of_face.as<int>(), head.as<long long>());
-  FACES_OK(hipGetLastError());
-  if (a.d_face_pixels) FACES_OK(hipMemcpyAsync(a.d_face_pixels, face_pixels.ptr, sizeof(int) * (size_t)nf, hipMemcpyDeviceToDevice, stream));
-  long long h_head[2] = {0, 0};
-  FACES_OK(hipMemcpyAsync(h_head, head.ptr, sizeof h_head, hipMemcpyDeviceToHost, stream));
-  FACES_OK(hipStreamSynchronize(stream));
-  const long long F = h_head[0];
-  if (F < 1 || F > nf) {
-    set_error("%s(): the grouping finds %lld carried faces of %d", kWho, F, nf);
-    return kLmError;
-  }
-  if (h_head[1] * L > INT_MAX) {  // one fit's candidates: a fit's count is an int
-    set_error("%s(): a face has %lld pixels, %lld candidate samples per fit: more than INT_MAX", kWho, h_head[1], h_head[1] * L);
-    return kLmError;
-  }
-  if (a.n_pixels) *a.n_pixels = S;
-  if (a.n_faces) *a.n_faces = F;
-
-  // ---- cosines of the carried faces ----
-  DevBuf angles_f;
-  if (!take(angles_f, sizeof(double) * 3 * (size_t)F * L, "the carried faces' cosines")) return kLmError;
-  if (cosines_run(a.d_vertices, a.d_faces, a.d_normals, face_list.as<int>(), F, a.leds, L, a.view, a.rv_mode, angles_f.as<double>(), stream) != 0)
-    return kLmError;
+  // ---- compact, group, cosines (capture_group.h) ----
+  CaptureGroup g;
+  if (capture_group_run(kWho, a, g) != 0) return kLmError;
+  if (g.S == 0) return 0;  // an empty capture: nothing is written but the pixel counts
+  const long long S = g.S, F = g.F, T = S * L;  // T: candidates of one channel
+  DevBuf &pixel_sorted = g.pixel_sorted, &face_sorted = g.face_sorted, &face_list = g.face_list, &face_first = g.face_first,
+         &rank_of_face = g.rank_of_face, &head = g.head, &angles_f = g.angles_f;
 
   // ---- count and pack ----
   const int pb = (int)((T + kCT - 1) / kCT), fits = (int)(3 * F);

@@ -33,6 +33,7 @@
 #include "fit_stats.h"
 #include "fit_host.h"
 #include "packed_plan.h"
+#include "weighted_fit.h"
 
 namespace brdf {
 
@@ -276,6 +277,9 @@ __global__ __launch_bounds__(kBlockThreads) void fit_stats_fold_kernel(StatsCtx 
   }
 }
 
+// ---- the weighted problem, n <= 16 (weighted_fit.h): a kernel, an argument block and a table of their own -------------------
+#include "fit_stats_weighted.inc"
+
 typedef void (*StatsKernel)(StatsCtx);
 // fast: the prepared-sample variant (exp(n log c) for pow(c, n)), an A/B switch only -- see stats_fast_path().  Ward's two paths
 // perform the same operations (brdf_models.h), so its `fast` entries are the exact kernels.
@@ -322,6 +326,19 @@ template <int M, int J, bool F>
 struct PartialK {
   static constexpr StatsKernel fn = fit_stats_partial_kernel<M, J, F>;
 };
+
+typedef void (*WeightedStatsKernel)(WeightedStatsCtx);
+WeightedStatsKernel pick_weighted(int model, int jac, bool fast) {  // (pick1's table: Ward's `fast` entries are the exact kernels)
+#define WK(M, J, F) fit_stats_weighted_rows_kernel<M, J, F>
+  static const WeightedStatsKernel t[2][MODEL_COUNT][3] = {{{WK(0, 0, false), WK(0, 1, false), WK(0, 2, false)},
+                                                           {WK(1, 0, false), WK(1, 1, false), WK(1, 2, false)},
+                                                           {WK(2, 0, false), WK(2, 1, false), WK(2, 2, false)}},
+                                                          {{WK(0, 0, true), WK(0, 1, true), WK(0, 2, true)},
+                                                           {WK(1, 0, true), WK(1, 1, true), WK(1, 2, true)},
+                                                           {WK(2, 0, false), WK(2, 1, false), WK(2, 2, false)}}};
+#undef WK
+  return t[fast ? 1 : 0][model][jac];
+}
 
 // BRDF_HIP_STATS_FAST=1: the A/B variant DESIGN.md section 2 measures (the pass is bound by fp64 issue, and pow is most of it).  It is
 // NOT the default and has no exact fallback: exp(n log c) is off pow(c, n) by up to |n log c| ulp of the specular term, which the
@@ -479,5 +496,51 @@ int stats_launches(const FitStatsArgs &a, const char *who, bool refused_large) {
   return 0;
 }
 }  // namespace
+
+// ---- the weighted problem (weighted_fit.h) -------------------------------------------------------------------------------------
+int weighted_stats_check(const WeightedStatsArgs &a, const char *who) {
+  if (fit_stats_check(a.stats, who) != 0) return kLmError;
+  if (a.stats.method != BRDF_METHOD_BC_DIF && a.stats.method != BRDF_METHOD_BC_DER) {
+    set_error("%s(): weights are limited to BRDF_METHOD_BC_DIF and BRDF_METHOD_BC_DER (got method %d)", who, a.stats.method);
+    return kLmError;
+  }
+  if (a.stats.n > 16) {
+    set_error("%s(): weights are limited to n <= 16 samples per fit (got n = %d)", who, a.stats.n);
+    return kLmError;
+  }
+  if (!a.d_w) {
+    set_error("%s(): null weights", who);
+    return kLmError;
+  }
+  return 0;
+}
+
+int weighted_stats_enqueue(const WeightedStatsArgs &wa, const char *who) {
+  if (weighted_stats_check(wa, who) != 0) return kLmError;
+  const FitStatsArgs &a = wa.stats;
+  WeightedStatsCtx c;
+  c.angles = a.d_angles;
+  c.x = a.d_x;
+  c.w = wa.d_w;
+  c.p = a.d_p;
+  c.extra = wa.d_extra_ss;
+  c.counts = a.d_counts;
+  c.nobs = wa.d_nobs;
+  c.covar = a.d_covar;
+  c.stats = a.d_stats;
+  c.rank = a.d_rank;
+  c.rows = a.S;
+  c.n = a.n;
+  const double d4 = a.opts ? a.opts[4] : LM_DIFF_DELTA;  // (stats_launches' reading of opts[4])
+  c.delta = d4 < 0.0 ? -d4 : d4;
+  MethodSpec ms;
+  (void)method_spec(a.method, &ms);
+  const int jac = ms.analytic ? JAC_ANALYTIC : (d4 < 0.0 ? JAC_CENTRAL : JAC_FORWARD);
+  (void)hipGetLastError();
+  const long long blocks = (c.rows + kRowsFits - 1) / kRowsFits;
+  hipLaunchKernelGGL(pick_weighted(a.model, jac, stats_fast_path()), dim3((unsigned)blocks), dim3(kRowsThreads), 0, a.stream, c);
+  STATS_OK(hipGetLastError());
+  return 0;
+}
 
 }  // namespace brdf

@@ -257,6 +257,80 @@ def fit_stats_batch(method: int, model: int, angles, x, p, *, opts=None, counts=
     return st
 
 
+def _weights_arg(w, x, torch):
+    _require(w.is_cuda and w.device == x.device and w.dtype == torch.float64 and tuple(w.shape) == tuple(x.shape),
+             "w: CUDA float64 [S,n] on the device of x")
+    return w.contiguous()
+
+
+def fit_batch_weighted(method: int, model: int, angles, x, w, p0, *, lb=None, ub=None, itmax=100, opts=None, counts=None):
+    """fit_batch with a weight per sample (brdf_hip_fit_batch_weighted_dev): fit s is levmar on sqrt(w) f against sqrt(w) x over its
+    first counts[s] samples.  n <= 16, METHOD_BC_DIF / METHOD_BC_DER only.  w: CUDA float64 [S,n]; the rest as fit_batch.  A weight
+    of 0 leaves a sample out of the sums (it still counts in n); a negative or non-finite counted weight refuses the fit (ret -1, zero
+    info, p as it came).  With w = 1 the result has the bytes of fit_batch(..., counts=counts).
+
+    Returns (p [S,3], info [S,10], ret [S] int32) as CUDA tensors; asynchronous on the current stream."""
+    import torch
+    _require(angles.is_cuda and x.is_cuda and p0.is_cuda and angles.device == x.device == p0.device, "angles, x, p0: CUDA tensors on one device")
+    _require(angles.dtype == torch.float64 and x.dtype == torch.float64 and p0.dtype == torch.float64, "angles, x, p0: float64")  # the kernels read raw doubles
+    _require(x.dim() == 2, "x must be [S, n]")
+    S, n = x.shape
+    _require(tuple(angles.shape) == (S, 3, n) and tuple(p0.shape) == (S, 3), "angles must be [S, 3, n], p0 [S, 3]")
+    w = _weights_arg(w, x, torch)
+    angles, x, p = angles.contiguous(), x.contiguous(), p0.contiguous()
+    info = torch.zeros((S, 10), dtype=torch.float64, device=x.device)
+    ret = torch.zeros((S,), dtype=torch.int32, device=x.device)
+    lb_a, ub_a, op_a = _f64(lb, 3), _f64(ub, 3), _f64(opts, 5)
+    if counts is not None:
+        counts = _counts_arg(counts, S, x.device, torch)
+    _call("brdf_hip_fit_batch_weighted_dev", x.device, method, model, angles.data_ptr(), x.data_ptr(), w.data_ptr(),
+          None if counts is None else counts.data_ptr(), S, n, p.data_ptr(), _dptr(lb_a), _dptr(ub_a), itmax, _dptr(op_a), info.data_ptr(),
+          ret.data_ptr(), _STREAM)
+    return p, info, ret
+
+
+def fit_stats_batch_weighted(method: int, model: int, angles, x, w, p, *, opts=None, counts=None, extra_ss=None, nobs=None) -> FitStats:
+    """fit_stats_batch for the weighted problem (brdf_hip_fit_stats_batch_weighted_dev; n <= 16, METHOD_BC_DIF / METHOD_BC_DER):
+    sumsq = sum w e^2, covar = sumsq / (nobs - 3) * inverse(J^T W J), R2 against sum w (x - weighted mean)^2.  extra_ss ([S] float64,
+    optional) is added to sumsq and to SStot; nobs ([S] int32, optional; default: the fit's count) is the observation count of the
+    degrees of freedom.  CUDA tensors (asynchronous on the current stream), or numpy arrays (host-pointer entry)."""
+    op_a = _f64(opts, 5)
+    if isinstance(x, np.ndarray):
+        angles, x, w, p = (np.ascontiguousarray(v, dtype=np.float64) for v in (angles, x, w, p))
+        _require(x.ndim == 2, "x must be [S, n]")
+        S, n = x.shape
+        _require(angles.shape == (S, 3, n) and p.shape == (S, 3) and w.shape == (S, n), "angles must be [S, 3, n], p [S, 3], w [S, n]")
+        counts, nobs = (None if v is None else np.ascontiguousarray(v, dtype=np.int32) for v in (counts, nobs))
+        extra_ss = None if extra_ss is None else np.ascontiguousarray(extra_ss, dtype=np.float64)
+        _require(all(v is None or v.shape == (S,) for v in (counts, nobs, extra_ss)), "counts, nobs, extra_ss must be [S]")
+        st = _zero_stats((S,))
+        _call("brdf_hip_fit_stats_batch_weighted", None, method, model, _dptr(angles), _dptr(x), _dptr(w), _iptr(counts), S, n, _dptr(p),
+              _dptr(op_a), _dptr(extra_ss), _iptr(nobs), _dptr(st.covar), _dptr(st.stats), _iptr(st.rank))
+        return st
+    import torch
+    _require(angles.is_cuda and x.is_cuda and p.is_cuda and angles.device == x.device == p.device, "angles, x, p: CUDA tensors on one device")
+    _require(angles.dtype == torch.float64 and x.dtype == torch.float64 and p.dtype == torch.float64, "angles, x, p: float64")  # the kernels read raw doubles
+    _require(x.dim() == 2, "x must be [S, n]")
+    S, n = x.shape
+    _require(tuple(angles.shape) == (S, 3, n) and tuple(p.shape) == (S, 3), "angles must be [S, 3, n], p [S, 3]")
+    w = _weights_arg(w, x, torch)
+    angles, x, p = angles.contiguous(), x.contiguous(), p.contiguous()
+    if counts is not None:
+        counts = _counts_arg(counts, S, x.device, torch)
+    if nobs is not None:
+        _require(nobs.is_cuda and nobs.device == x.device and nobs.dtype == torch.int32 and tuple(nobs.shape) == (S,), "nobs: CUDA int32 [S] on the device of x")
+        nobs = nobs.contiguous()
+    if extra_ss is not None:
+        _require(extra_ss.is_cuda and extra_ss.device == x.device and extra_ss.dtype == torch.float64 and tuple(extra_ss.shape) == (S,),
+                 "extra_ss: CUDA float64 [S] on the device of x")
+        extra_ss = extra_ss.contiguous()
+    st = _zero_stats((S,), x.device)
+    _call("brdf_hip_fit_stats_batch_weighted_dev", x.device, method, model, angles.data_ptr(), x.data_ptr(), w.data_ptr(),
+          None if counts is None else counts.data_ptr(), S, n, p.data_ptr(), _dptr(op_a), None if extra_ss is None else extra_ss.data_ptr(),
+          None if nobs is None else nobs.data_ptr(), st.covar.data_ptr(), st.stats.data_ptr(), st.rank.data_ptr(), _STREAM)
+    return st
+
+
 def pack_samples(angles, x, counts):
     """Padded rows -> a packed batch: angles [S,3,n], x [S,n], counts [S] (integers; torch tensors on one device, or numpy arrays)
     -> (angles [3 * total] float64, x [total], offsets [S+1] int64) of the same kind, total = sum(counts).  Fit s's first counts[s]
@@ -602,6 +676,117 @@ def group_capture_samples(images, pixel_map, face_angles, model: int, *, v_min: 
     cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0)  # noqa: E731
     return (np.ascontiguousarray(cat(angles), dtype=np.float64), np.ascontiguousarray(cat(x), dtype=np.float64), np.array(offsets, dtype=np.int64),
             np.array(fit_face, dtype=np.int32), np.array(fit_channel, dtype=np.int32), face_pixels)
+
+
+class CaptureMeans(NamedTuple):
+    """What fit_capture_means returns: fit_capture_faces' maps and one more."""
+    surfaces: object     # [nf,3,3] float64: {kd, ks, n} per face and channel
+    info: object         # [nf,3,10] float64: levmar's info[] of the weighted fit (info[1]: the weighted objective, without `within`)
+    ret: object          # [nf,3] int32: iterations, or -1
+    stats: FitStats | None  # the full-sample statistics: covar [nf,3,3,3], stats [nf,3,8], rank [nf,3]; None without want_stats
+    count: object        # [nf,3] int32: k, the samples of the fit
+    lights: object       # [nf,3] int32: the lights with a sample, the weighted fit's n
+    face_pixels: object  # [nf] int32: the pixels that carry the face (0 where none)
+    avg: np.ndarray      # [3]
+    n_pixels: int
+    n_faces: int
+
+
+def fit_capture_means(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, v_min: int = 0, v_max: int = 255,
+                      cos_min: float = -2.0, rv_mode: int = 0, p0=(0.5, 1.0, 1.0), lb=(0.0, 0.0, 0.0), ub=(100.0, 100.0, 100.0),
+                      itmax: int = 100, opts=None, want_stats: bool = True, validate: bool = True, out: CaptureMeans | None = None) -> CaptureMeans:
+    """fit_capture_faces as a weighted fit of per-light means (brdf_hip_fit_capture_means_dev; L <= 16): all pixels of a face share its
+    cosines, so the fit of a face's k samples and the fit of its at most L per-light means, weighted by the lights' sample counts, have
+    the same minimiser -- capture_light_means is the definition as code.  Same candidates and validity rule as fit_capture_faces.
+    `info` is the weighted fit's; `stats` (sumsq, covariance with k - 3 degrees of freedom, sigma, rho, R2) are the full-sample ones.
+    Fewer than 3 lights with a sample: ret -1, zero info, p0 in surfaces, rank 0.  The call waits for the stream."""
+    import torch
+    args, keep, nf = _capture_args(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, rv_mode, p0, lb, ub, itmax, opts,
+                                   validate)
+    dev = keep[0].device
+    if out is None:
+        def z(*shape, dtype=torch.float64):
+            return torch.zeros((nf, *shape), dtype=dtype, device=dev)
+        out = CaptureMeans(z(3, 3), z(3, 10), z(3, dtype=torch.int32), _zero_stats((nf, 3), dev) if want_stats else None, z(3, dtype=torch.int32),
+                           z(3, dtype=torch.int32), z(dtype=torch.int32), None, 0, 0)
+    _require(not want_stats or out.stats is not None, "out: want_stats needs out.stats")
+    st = out.stats if want_stats else None
+    maps = [(out.surfaces, (nf, 3, 3), torch.float64), (out.info, (nf, 3, 10), torch.float64), (out.ret, (nf, 3), torch.int32),
+            (out.count, (nf, 3), torch.int32), (out.lights, (nf, 3), torch.int32), (out.face_pixels, (nf,), torch.int32)]
+    if st is not None:
+        maps += [(st.covar, (nf, 3, 3, 3), torch.float64), (st.stats, (nf, 3, 8), torch.float64), (st.rank, (nf, 3), torch.int32)]
+    for t, shape, dtype in maps:
+        _require(t.is_cuda and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(),
+                 f"out: contiguous CUDA {dtype} {list(shape)} tensors on the capture's device")
+    avg = np.zeros(3)
+    npx, nfc = C.c_longlong(0), C.c_longlong(0)
+    _call("brdf_hip_fit_capture_means_dev", dev, *args, int(v_min), int(v_max), float(cos_min), out.surfaces.data_ptr(), out.info.data_ptr(),
+          out.ret.data_ptr(), None if st is None else st.covar.data_ptr(), None if st is None else st.stats.data_ptr(),
+          None if st is None else st.rank.data_ptr(), out.count.data_ptr(), out.lights.data_ptr(), out.face_pixels.data_ptr(), _dptr(avg),
+          C.byref(npx), C.byref(nfc), _STREAM)
+    return CaptureMeans(out.surfaces, out.info, out.ret, st, out.count, out.lights, out.face_pixels, avg, npx.value, nfc.value)
+
+
+class LightMeans(NamedTuple):
+    """What capture_light_means returns: the weighted batch of fit_capture_means, rows of stride L (NumPy)."""
+    angles: np.ndarray       # [fits,3,L] float64: the face's cosines at the lights with a sample, ascending; NaN behind counts
+    x: np.ndarray            # [fits,L] float64: the lights' means S1 / (255 c)
+    w: np.ndarray            # [fits,L] float64: the lights' sample counts c
+    counts: np.ndarray       # [fits] int32: the lights with a sample
+    k: np.ndarray            # [fits] int32: the samples, sum c
+    within: np.ndarray       # [fits] float64: sum_l (c S2 - S1^2) / (65025 c)
+    fit_face: np.ndarray     # [fits] int32
+    fit_channel: np.ndarray  # [fits] int32
+    face_pixels: np.ndarray  # [nf] int32
+
+
+def capture_light_means(images, pixel_map, face_angles, model: int, *, v_min: int = 0, v_max: int = 255, cos_min: float = -2.0) -> LightMeans:
+    """The host twin of fit_capture_means' accumulation (NumPy, no device): its definition as code.  Arguments, fits (ascending face,
+    then channel), candidates and validity rule as group_capture_samples.  Per fit and light l with c_l > 0 valid values v:
+    x_l = sum v / (255 c_l), w_l = c_l; the lights with a sample in ascending order at the front of rows of stride L; k = sum c_l;
+    within = sum_l (c_l sum v^2 - (sum v)^2) / (65025 c_l), the numerator in integers, added in ascending light order."""
+    images, pixel_map = np.asarray(images), np.asarray(pixel_map)
+    face_angles = np.ascontiguousarray(face_angles, dtype=np.float64)
+    _require(images.ndim == 4 and images.shape[3] == 3 and images.dtype == np.uint8 and pixel_map.shape == images.shape[1:3],
+             "images [L,H,W,3] uint8, pixel_map [H,W]")
+    L, H, W = images.shape[:3]
+    _require(face_angles.ndim == 3 and face_angles.shape[1:] == (3, L), "face_angles [nf,3,L]")
+    _require(model in (MODEL_PHONG, MODEL_BLINN_PHONG, MODEL_WARD), "unknown model")
+    nf = face_angles.shape[0]
+    reads = [True, model != MODEL_PHONG, model != MODEL_BLINN_PHONG]  # the planes the model reads
+    face_pixels = np.zeros(nf, dtype=np.int32)
+    values = {}  # face -> [L, pixels, 3] int64
+    for f in range(nf):
+        ys, xs = np.nonzero(pixel_map == f)
+        face_pixels[f] = ys.size
+        if ys.size:
+            values[f] = images[:, H - 1 - ys, xs, :].astype(np.int64)
+    fits = 3 * len(values)
+    angles, x, w = np.full((fits, 3, L), np.nan), np.full((fits, L), np.nan), np.full((fits, L), np.nan)
+    counts, k, within = np.zeros(fits, dtype=np.int32), np.zeros(fits, dtype=np.int32), np.zeros(fits)
+    fit_face, fit_channel = np.zeros(fits, dtype=np.int32), np.zeros(fits, dtype=np.int32)
+    s = 0
+    for f in sorted(values):
+        cos_ok = np.all([face_angles[f, j, :] > cos_min for j in range(3) if reads[j]], axis=0)  # [L]
+        for ch in range(3):
+            fit_face[s], fit_channel[s] = f, ch
+            n = 0
+            for l in range(L):
+                v = values[f][l, :, ch]
+                v = v[(v >= v_min) & (v <= v_max)] if cos_ok[l] else v[:0]
+                c = int(v.size)
+                if c == 0:
+                    continue
+                s1, s2 = int(v.sum()), int((v * v).sum())
+                angles[s, :, n] = face_angles[f, :, l]
+                x[s, n] = float(s1) / (255.0 * float(c))
+                w[s, n] = float(c)
+                within[s] += float(c * s2 - s1 * s1) / (65025.0 * float(c))
+                k[s] += c
+                n += 1
+            counts[s] = n
+            s += 1
+    return LightMeans(angles, x, w, counts, k, within, fit_face, fit_channel, face_pixels)
 
 
 def fit_capture_single(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, rv_mode: int = 0,

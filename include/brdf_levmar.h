@@ -241,7 +241,8 @@ int brdf_hip_last_multi_stats(int shard, int *device, long long *first, long lon
  * pointers, each output may be NULL (not all three); opts (5 or NULL): HOST, only opts[4] is read.  n >= 3.  All sums are
  * fixed-order trees: two calls give the same bits, and a fit's result does not depend on S or on its place in the batch.
  * Asynchronous on `stream`.  Arguments are checked before any HIP call.  Returns 0, or LM_ERROR with a message in
- * brdf_hip_last_error().  Not covered: dscl, weights, a multi-GPU variant (call the host-pointer entry per device). */
+ * brdf_hip_last_error().  Not covered: dscl, a multi-GPU variant (call the host-pointer entry per device); weights only in
+ * brdf_hip_fit_stats_batch_weighted_dev below (n <= 16). */
 #define BRDF_STATS_SZ 8
 int brdf_hip_fit_stats_batch_dev(int method, int model, const double *d_angles, const double *d_x, int S, int n,
                                  const double *d_p, const double *opts, double *d_covar, double *d_stats, int *d_rank,
@@ -275,7 +276,7 @@ int brdf_hip_fit_stats_batch(int method, int model, const double *angles, const 
  *               with S = 1, n = counts[s].  Both synchronise the stream.
  *   Checks      everything the host can see (null pointers, S or n <= 0, unknown model / method, lb > ub) is checked before any
  *               HIP call.
- * Not covered: per-sample weights (a different definition: levmar on sqrt(w) f), dscl, brdf_hip_fit_batch_multi. */
+ * Not covered: dscl, brdf_hip_fit_batch_multi; per-sample weights only as below (n <= 16, dlevmar_bc_dif / dlevmar_bc_der). */
 int brdf_hip_fit_batch_ragged_dev(int method, int model, const double *d_angles, const double *d_x, const int *d_counts, int S, int n,
                                   double *d_p, const double *lb, const double *ub, int itmax, const double *opts, double *d_info,
                                   int *d_ret, void *stream);
@@ -286,6 +287,42 @@ int brdf_hip_fit_stats_batch_ragged_dev(int method, int model, const double *d_a
                                         void *stream);
 int brdf_hip_fit_stats_batch_ragged(int method, int model, const double *angles, const double *x, const int *counts, int S, int n,
                                     const double *p, const double *opts, double *covar, double *stats, int *rank);
+
+/* ---- per-sample weights, n <= 16 (extensions) --------------------------------------------------------------- */
+/* The ragged batch above with a weight per sample, in ONE size class: n <= 16 (the application's own: 16 lights per surfel) and
+ * BRDF_METHOD_BC_DIF / BRDF_METHOD_BC_DER.
+ *   Definition  fit s is levmar (dlevmar_bc_dif, or dlevmar_bc_der with the device Jacobian) on the weighted problem
+ *               hx_i = sqrt(w_i) f_i(p), x'_i = sqrt(w_i) x_i over the first counts[s] samples of its rows: what a levmar caller
+ *               does today by scaling inside the callback.  info[1] = sum w_i (x_i - f_i(p))^2.
+ *   Layout      d_w[S][n] has the layout of d_x; d_counts[S] as in the ragged call, or NULL: every fit has n samples.
+ *   Unit weights  w = 1.0 everywhere returns the BYTES of brdf_hip_fit_batch_ragged_dev (the statistics: of
+ *               brdf_hip_fit_stats_batch_ragged_dev): every operation the weights add is exact then.
+ *   Zero        a weight of 0 is a sample that contributes nothing and still counts in n.
+ *   Refused     a fit whose counted samples include a weight that is negative or not finite is refused as n < m is: ret[s] =
+ *               LM_ERROR, info[s] all zeros, p[s] as it came.  Nothing at or behind counts[s] is read.
+ *   Statistics  at d_p[s], with J the Jacobian of the weighted problem as `method` forms it:  sumsq = sum w e^2 (+ extra_ss[s]);
+ *               covar = sumsq / (nobs[s] - 3) * inverse(J^T W J);  R2 = 1 - sumsq / SStot, SStot = sum w (x - mean)^2 (+ extra_ss[s]),
+ *               mean = sum w x / sum w;  sd, rho and rank as in brdf_hip_fit_stats_batch_dev.  d_extra_ss[S] (DEVICE, may be NULL)
+ *               is a sum of squares that does not depend on p -- for a fit of group means weighted by the groups' sizes, the
+ *               spread of the observations inside their groups, which makes sumsq, covar and R2 those of the fit of all
+ *               observations.  d_nobs[S] (DEVICE, may be NULL: the fit's count) is the observation count of the degrees of freedom.
+ *               A count below 3: rank 0 as in the ragged pass; a negative or non-finite weight: rank 0, sumsq and R2 not finite.
+ *   Checks      refused before any HIP call, under the entry's own name: n > 16, a method other than BRDF_METHOD_BC_DIF /
+ *               BRDF_METHOD_BC_DER, NULL weights, and everything the ragged entries refuse.
+ * The host-pointer twins upload, run, download and synchronise; brdf_hip_fit_batch_weighted returns the number of fits that ended in
+ * LM_ERROR.  Not covered: weights above 16 samples per fit, for dlevmar_dif / dlevmar_der, and in the packed, multi-GPU and
+ * single-fit calls; dscl. */
+int brdf_hip_fit_batch_weighted_dev(int method, int model, const double *d_angles, const double *d_x, const double *d_w, const int *d_counts,
+                                    int S, int n, double *d_p, const double *lb, const double *ub, int itmax, const double *opts,
+                                    double *d_info, int *d_ret, void *stream);
+int brdf_hip_fit_batch_weighted(int method, int model, const double *angles, const double *x, const double *w, const int *counts, int S, int n,
+                                double *p, const double *lb, const double *ub, int itmax, const double *opts, double *info, int *ret);
+int brdf_hip_fit_stats_batch_weighted_dev(int method, int model, const double *d_angles, const double *d_x, const double *d_w,
+                                          const int *d_counts, int S, int n, const double *d_p, const double *opts, const double *d_extra_ss,
+                                          const int *d_nobs, double *d_covar, double *d_stats, int *d_rank, void *stream);
+int brdf_hip_fit_stats_batch_weighted(int method, int model, const double *angles, const double *x, const double *w, const int *counts, int S,
+                                      int n, const double *p, const double *opts, const double *extra_ss, const int *nobs, double *covar,
+                                      double *stats, int *rank);
 
 /* ---- packed batches: fits of any size in one call (extensions) --------------------------------------------- */
 /* S fits laid back to back, CSR style, bucketed by size class (<= 16, 64, 256, 1024, 4096 samples, and above) inside the library:
@@ -314,7 +351,7 @@ int brdf_hip_fit_stats_batch_ragged(int method, int model, const double *angles,
  *               offsets that decrease and a fit of more than INT_MAX samples -- are refused before any HIP call.
  *   Host entries  upload the offsets[S] - offsets[0] samples the batch covers; brdf_hip_fit_batch_packed returns the number of fits
  *               that ended in LM_ERROR (refused ones included), as brdf_hip_fit_batch does.
- * Not covered: per-sample weights, dscl, a packed brdf_hip_fit_batch_multi. */
+ * Not covered: per-sample weights (n <= 16 only: brdf_hip_fit_batch_weighted_dev), dscl, a packed brdf_hip_fit_batch_multi. */
 int brdf_hip_fit_batch_packed_dev(int method, int model, const double *d_angles, const double *d_x, const long long *d_offsets, int S,
                                   double *d_p, const double *lb, const double *ub, int itmax, const double *opts, double *d_info, int *d_ret,
                                   long long workspace_bytes, void *stream);
@@ -448,8 +485,8 @@ int brdf_hip_fit_capture_masked_dev(int model, const unsigned char *d_images, in
  *                  pixels x L > INT_MAX.  An allocation that fails returns LM_ERROR with the bytes asked for in the message.
  *   Empty capture  no carried face: returns 0 with n_pixels = n_faces = 0 and a zero avg; nothing is written but d_face_pixels.
  * Synchronises `stream` before returning.  Returns 0, or LM_ERROR with a message that names the entry in brdf_hip_last_error().
- * Not covered: the count-weighted fit of per-light means (the same minimiser; it needs per-sample weights, which the library does not
- * have) and a grouped brdf_hip_fit_capture_single_dev. */
+ * The count-weighted fit of per-light means -- the same minimiser from at most L samples per fit -- is brdf_hip_fit_capture_means_dev
+ * below (L <= 16).  Not covered: a grouped brdf_hip_fit_capture_single_dev. */
 int brdf_hip_fit_capture_faces_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
                                    const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
                                    const double *view_origin, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
@@ -457,6 +494,42 @@ int brdf_hip_fit_capture_faces_dev(int model, const unsigned char *d_images, int
                                    double *d_brdf_surfaces, double *d_surface_info, int *d_surface_ret, double *d_surface_covar,
                                    double *d_surface_stats, int *d_surface_rank, int *d_surface_count, int *d_face_pixels, double *avg,
                                    long long *n_pixels, long long *n_faces, void *stream);
+
+/* brdf_hip_fit_capture_faces_dev as a WEIGHTED fit of per-light means.  All pixels of a face share the face's cosines, so the model
+ * values f_l(p) are the same for every pixel of the face, and with c_l valid values v_pl under light l and their mean m_l
+ *     sum_{p,l} (v_pl / 255 - f_l(p))^2  =  sum_l c_l (m_l - f_l(p))^2  +  within,   within = sum_{p,l} (v_pl / 255 - m_l)^2,
+ * where `within` does not depend on p: the fit of the k = sum c_l samples and the fit of at most L means weighted by c_l have the same
+ * minimiser and the same J^T J.  The weighted fit has n <= 16 whatever the face's pixel count (brdf_hip_fit_batch_weighted_dev).
+ * Arguments and maps are brdf_hip_fit_capture_faces_dev's, without workspace_bytes, with one more optional map:
+ *   Which fits, candidates, validity rule   those of brdf_hip_fit_capture_faces_dev, word for word (a NaN cosine is never a sample).
+ *   Samples        of fit (f, c): the lights with at least one valid value, in ascending order: the face's cosines at that light,
+ *                  x = S1 / (255 c), w = c, with c, S1 = sum v and S2 = sum v^2 accumulated as INTEGERS (their order cannot show: two
+ *                  calls give the same bytes; no float atomics anywhere).  k = sum c;  within = sum_l (c S2 - S1^2) / (65025 c), the
+ *                  numerator exactly in 64-bit integers, one division per light, added in ascending light order.
+ *   Result         d_brdf_surfaces, d_surface_info, d_surface_ret: brdf_hip_fit_batch_weighted_dev (BRDF_METHOD_BC_DIF) on those rows
+ *                  from p0.  info[1] is the WEIGHTED objective sum_l c_l (m_l - f_l(p))^2, without `within`.
+ *   Statistics     brdf_hip_fit_stats_batch_weighted_dev with extra_ss = within and nobs = k: stats[0] = info[1] + within,
+ *                  the covariance (k - 3 degrees of freedom), sigma, rho and R2 are the FULL-SAMPLE ones -- in exact
+ *                  arithmetic brdf_hip_fit_capture_faces_dev's at the same p.
+ *   Maps           d_surface_count[nf][3] = k, the fit's samples; d_surface_lights[nf][3] (DEVICE, may be NULL) = the lights with a
+ *                  sample, the weighted fit's n; the rest as brdf_hip_fit_capture_faces_dev.  avg in a fixed order.
+ *   Too few        fewer than 3 lights with a sample is levmar's n < m refusal: ret = LM_ERROR, info all zeros, p0 in d_brdf_surfaces,
+ *                  rank 0 -- also where k >= 3: three samples under two lights do not determine three parameters here.  (L < 3: every
+ *                  fit is refused and the statistics maps hold zeros.)
+ *   One pixel      a face of one pixel under the rule switched off has weights 1, means v / 255, within = 0 and k = L: the bytes of
+ *                  brdf_hip_fit_capture_faces_dev.
+ *   Memory         per (carried face, channel, light) 20 bytes of integer sums and 40 bytes of the weighted rows, plus the grouping's
+ *                  24 bytes per carried pixel and the sort's scratch.  No per-candidate array.
+ *   Refused before any HIP call, under the entry's name: what brdf_hip_fit_capture_faces_dev refuses, and L outside [1, 16] (16 < L
+ *                  <= 64 is brdf_hip_fit_capture_faces_dev's).  Refused once the counts are known: a face of more than 11 000 000
+ *                  pixels (its sums of squares would leave 64-bit integers).
+ * Synchronises `stream` before returning.  Returns 0, or LM_ERROR with a message that names the entry in brdf_hip_last_error(). */
+int brdf_hip_fit_capture_means_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                   const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                   const double *view_origin, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
+                                   const double *opts, int v_min, int v_max, double cos_min, double *d_brdf_surfaces, double *d_surface_info,
+                                   int *d_surface_ret, double *d_surface_covar, double *d_surface_stats, int *d_surface_rank, int *d_surface_count,
+                                   int *d_surface_lights, int *d_face_pixels, double *avg, long long *n_pixels, long long *n_faces, void *stream);
 
 /* Replaces CBRDFdata::CalcBRDFEquation_SingleBRDF (brdfdata.cpp:1138-1186) with SolveEquation_SingleBRDF (:992-1062): ONE
  * {kd, ks, n} per colour channel for the whole object, fitted with dlevmar_bc_dif to the L samples of every face the pixel
