@@ -245,6 +245,21 @@ struct PassUniforms {
       nq = Mdl::nl(r.q);
     }
   }
+
+  // The uniforms of the RQ_DIF_TRIAL request DifMachine::fused_trial_step issues, from the request's values alone (the step hands
+  // them out of its registers: DifMachine::NextTrial): every field gets the bytes build(req, need_base = false, analytic_jac)
+  // leaves for that request -- whose central and scal are clear_req()'s 0 and 1 -- and no other field is touched
+  // (tests/cpp/trial_uniforms_harness.cpp compares the two after every step of whole fits).
+  LM_HD void build_trial(const double *q, const double *dpv, double dpl2, bool analytic_jac = false) {
+    ncand = 0;
+    analytic = analytic_jac ? 1 : 0;
+    central = 0;
+    scal = 1.0;
+    dp_l2 = dpl2;
+    for (int j = 0; j < kM; ++j) dp[j] = dpv[j];
+    lq = Mdl::lin(q);
+    nq = Mdl::nl(q);
+  }
 };
 
 // f(p) for one (prepared) sample

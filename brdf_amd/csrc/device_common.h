@@ -208,11 +208,12 @@ __device__ __forceinline__ void expand_trial_sums(const Core &core, const Cool &
 // in one straight-line block (lm_machine.h).  false: nothing was written (sums[] included) -- expand_trial_sums + run() as ever.
 template <class Machine>
 __device__ __forceinline__ bool fused_trial_step_device(const typename Machine::Cold &c, typename Machine::CoreInts &hi, typename Machine::CoreReals &h,
-                                                        typename Machine::Cool &cool, Request<kM> &req, const double *sums, const double *dpv) {
+                                                        typename Machine::Cool &cool, Request<kM> &req, const double *sums, const double *dpv,
+                                                        typename Machine::NextTrial *next = nullptr) {
   if (hi.phase != Machine::D_AFTER_TRIAL) return false;
   double out[SumLayout<kM>::DIF_TRIAL];
   expand_trial_sums_to(h, cool, dpv, sums, out);
-  return Machine::template fused_trial_step<true, true>(c, hi, h, cool, req, out);
+  return Machine::template fused_trial_step<true, true>(c, hi, h, cool, req, out, next);
 }
 
 

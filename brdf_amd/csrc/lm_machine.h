@@ -479,8 +479,14 @@ struct DifMachine {
   // state after every step).  Anything else -- a stop, a fresh Jacobian due, a rejection without an update, a failed
   // solve -- returns false with the machine untouched, and run() does the step: the rare paths exist once.
   // s: the trial pass's sums (SumLayout::DIF_TRIAL); never aliases the machine (callers pass a local array or sums[]).
+  // next (optional): the values of the trial request the step issues, handed out from its locals -- a caller that forms the next
+  // pass's uniforms from them (PassUniforms::build_trial) need not read the request back.  Written only when the step is taken.
+  struct NextTrial {
+    Real q[M], dp[M], dp_l2;
+  };
   template <bool ONE_LANE = false, bool MULTI = false>
-  static LM_HD bool fused_trial_step(const Cold &c, CoreInts &hi, CoreReals &h, Cool &cool, Request<M, Real> &req, const Real *s) {
+  static LM_HD bool fused_trial_step(const Cold &c, CoreInts &hi, CoreReals &h, Cool &cool, Request<M, Real> &req, const Real *s,
+                                     NextTrial *next = nullptr) {
     constexpr int NL = SumLayout<M>::NL;
     if (hi.phase != D_AFTER_TRIAL || !c.speculative || hi.stop) return false;
     // ---- D_AFTER_TRIAL
@@ -551,6 +557,13 @@ struct DifMachine {
     if (ONE_LANE) ok = lm_uniform(ok);
     if (!ok) return false;
     // ---- every test has passed: commit
+    if (next) {
+      for (int i = 0; i < M; ++i) {
+        next->q[i] = pdpn[i];
+        next->dp[i] = dpn[i];
+      }
+      next->dp_l2 = dp_l2;
+    }
     hi.k = k1;
     hi.nu = nu;
     ++hi.nfev;

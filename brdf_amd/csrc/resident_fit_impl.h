@@ -23,9 +23,10 @@
 // misc_core.c:153-171 + lm_core.c:617-653) therefore moves no sample bytes at all.  Passes are separated by an
 // in-launch exchange of the per-workgroup partial sums instead of a kernel boundary:
 //
-//   all waves    : sweep -> reduction over the eight waves -> <= 14 partial sums in LDS            (barriers X1, X2)
-//   control wave : publishes them as tagged 16-byte cells {lo32, tag, hi32, tag}, each ONE write-through (sc1)
-//                  store; gathers everybody's in two levels (control_exchange below); folds in a fixed order;
+//   all waves    : sweep -> reduction over the eight waves (barrier X1); the wave that finishes a partial sum publishes it as a
+//                  tagged 16-byte cell {lo32, tag, hi32, tag}, ONE write-through (sc1) store (worker_reduce).  (A fit of one
+//                  workgroup, and the batched kernels: <= 14 partial sums in LDS behind barrier X2, no exchange.)
+//   control wave : gathers everybody's cells in two levels (control_exchange below); folds in a fixed order;
 //                  steps ITS OWN copy of the LM state machine (lm_machine.h) -- the same redundant execution as in
 //                  the launch chain of stream_fit.hip, so there is no broadcast hop -- in LDS (a register copy of
 //                  the machine's busy half was measured and lost, see the control wave's comment below); builds the
@@ -179,13 +180,51 @@ __device__ __forceinline__ void for_samples(int nk, F &&f) {
   }
 }
 
+// ---- the exchange tables' geometry and cells (the exchange itself: control_exchange below; the reducing waves publish into them) ----
+constexpr int kGroup = 16;
+constexpr int kMaxGroups = 16;  // >= ceil(#CUs / kGroup); also the width of a level-2 row
+constexpr int kReplicas = 8;
+constexpr size_t kBlockGranules = (size_t)kRowWords * kGroup;                    // one group's rows / one copy of the group rows
+constexpr size_t kRowsGranules = 2 * (size_t)kMaxGroups * kBlockGranules;         // [parity][group]
+constexpr size_t kGroupsGranules = 2 * (size_t)kReplicas * kBlockGranules;        // [parity][replica]
+
+// A value travels as ONE 16-byte cell = two granules {lo32, tag | hi32, tag}, written by one write-through (sc1) store and
+// read by one sc1 load: a scalar sc1 store is one fabric write whatever its size, so 8-byte stores cost 2.7x the time per
+// byte of 16-byte ones (MI355X_MICROARCH.md, inter-workgroup visibility table) -- a leader publishes up to 14 x 8 cells
+// per pass.  Each half carries its own tag, so a cell torn between its halves is simply "not ready yet".
+// A block is [slot][16 columns] cells.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+constexpr int kCacheSc1 = 16;  // aux bits of the gfx940+ buffer instructions: sc1
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t table_rsrc(const u64 *p, size_t granules) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<u64 *>(p), 0, (int)(granules * sizeof(u64)), 0x00027000);
+}
+__device__ __forceinline__ void put_cell(__amdgpu_buffer_rsrc_t t, unsigned cell, unsigned tag, double v) {
+  const u32x4 d = {(unsigned)__double2loint(v), tag, (unsigned)__double2hiint(v), tag};
+  __builtin_amdgcn_raw_buffer_store_b128(d, t, (int)(cell * 16u), 0, kCacheSc1);
+}
+
 // Reduction of NS sums and one max over the eight waves: two DPP steps inside each row of 16 lanes leave the sum of
 // every 4 consecutive lanes in lanes 3,7,11,..; those park their values as buf[slot][thread/4]; wave w then owns slots
 // {w, w+8}: each lane adds its two entries and one DPP tree per slot finishes it.  A pure function of NS: reproducible.
 // MAX = false (dlevmar_dif: its machine never looks at max |e|): no max slot -- one value less per wave, one 16-byte cell less
 // per row and, with nine sums, one of the four gather instructions of an exchange
-template <int NS, bool MAX = true>
-__device__ __forceinline__ void worker_reduce(const double *acc, double mx, double *buf, double *out, long long *st_, long long &last_) {
+//
+// PUB (a single fit spread over several workgroups, pub.on): nobody in this workgroup reads its pre-exchange sums -- only the
+// other workgroups do, through the row table.  So the lane that finishes a slot stores that slot's cell itself (the cell, tag
+// and store control_exchange() would use: cells are self-validating, any wave may write one) and there is no out[] store, no
+// barrier X2 and no read-back by the control wave between the last DPP step and the publish.  All eight waves skip X2 alike;
+// red[] has no writer before the next pass's stage 1, behind barrier B.
+struct RowPublish {
+  const u64 *rows;  // ResidentCtx::rows
+  unsigned cell0;   // this workgroup's column of its group's block of this epoch's parity: slot v is cell cell0 + v * kGroup
+  unsigned tag;
+  bool on;          // the grid has more than one workgroup
+  bool withhold;    // test hook (ResidentCtx::sabotage_epoch): this workgroup publishes nothing this epoch
+};
+
+template <int NS, bool MAX = true, bool PUB = false>
+__device__ __forceinline__ void worker_reduce(const double *acc, double mx, double *buf, double *out, const RowPublish &pub, long long *st_,
+                                              long long &last_) {
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x >> 6;  // 0..7
   double v[NS + 1];
@@ -231,6 +270,16 @@ __device__ __forceinline__ void worker_reduce(const double *acc, double mx, doub
     } else {
       wave_reduce2_to_last<OpMax, OpSum>(s0, s1);
     }
+    if constexpr (PUB) {
+      if (pub.on) {
+        if (lane == kWave - 1 && !pub.withhold) {
+          const __amdgpu_buffer_rsrc_t rows = table_rsrc(pub.rows, kRowsGranules);
+          if (has0) put_cell(rows, pub.cell0 + (max0 ? kSums : k0) * kGroup, pub.tag, s0);
+          if (has1) put_cell(rows, pub.cell0 + (max1 ? kSums : k1) * kGroup, pub.tag, s1);
+        }
+        return;
+      }
+    }
     if (lane == kWave - 1) {
       if (has0) out[max0 ? kSums : k0] = s0;
       if (has1) out[max1 ? kSums : k1] = s1;
@@ -239,13 +288,21 @@ __device__ __forceinline__ void worker_reduce(const double *acc, double mx, doub
   __syncthreads();  // X2
 }
 
+// the RowPublish of this workgroup at `epoch` (the cell and tag arithmetic of control_exchange())
+__device__ __forceinline__ RowPublish row_publish(const ResidentCtx &ctx, unsigned epoch) {
+  const unsigned grp = blockIdx.x / kGroup;
+  return RowPublish{ctx.rows, ((epoch & 1u) * kMaxGroups + grp) * (kSlots * kGroup) + blockIdx.x % kGroup, ctx.tag_base + epoch + 1u, gridDim.x > 1,
+                    (int)epoch == ctx.sabotage_epoch && blockIdx.x == gridDim.x - 1};
+}
+
 // The exchange, executed by the control wave: a two-level gather.  (A flat all-gather -- every workgroup reading all
 // 256 rows -- was measured at 6.2 us: 256 readers per line make the few hundred lines of the row table a hot spot
 // of the memory side; more loads in flight per reader made it slower, not faster.)
 //
 //   level 1  rows [parity][group][slot][member]: workgroups are grouped 16 by 16 and a group's 14 slots x 16 members
-//            are 3.5 KB of CONSECUTIVE 16-byte cells.  Every workgroup publishes its NS sums + max (lanes 0..NS-1 and
-//            lane 13, one cell each).  One workgroup of a group is its leader (a different
+//            are 3.5 KB of CONSECUTIVE 16-byte cells.  Every workgroup publishes its NS sums + max, one cell each (slot kSums
+//            is the max's): lane 63 of the wave that reduced the slot, or -- !PUBLISHED, the channel kernel -- lanes 0..NS-1
+//            and lane 13 of the control wave, from sums[].  One workgroup of a group is its leader (a different
 //            position in every group, so that the leaders -- blockIdx % 8 tells which workgroups share an XCD -- are spread
 //            over the XCDs).  ALL 64 lanes of its control wave gather: lane l takes member l % 16 of slot 4j + l / 16,
 //            j = 0..3 (a wave load instruction reads 1 KB = 8 whole lines; 4 instructions fetch a TRIAL row set), so the 16
@@ -258,28 +315,6 @@ __device__ __forceinline__ void worker_reduce(const double *acc, double mx, doub
 //            <= 16 group rows of copy blockIdx % replicas the same way and folds them: identical bits everywhere.
 //
 // A gather re-reads its block until every tag matches; false = wait abandoned (spin budget, or somebody else gave up).
-constexpr int kGroup = 16;
-constexpr int kMaxGroups = 16;  // >= ceil(#CUs / kGroup); also the width of a level-2 row
-constexpr int kReplicas = 8;
-constexpr size_t kBlockGranules = (size_t)kRowWords * kGroup;                    // one group's rows / one copy of the group rows
-constexpr size_t kRowsGranules = 2 * (size_t)kMaxGroups * kBlockGranules;         // [parity][group]
-constexpr size_t kGroupsGranules = 2 * (size_t)kReplicas * kBlockGranules;        // [parity][replica]
-
-// A value travels as ONE 16-byte cell = two granules {lo32, tag | hi32, tag}, written by one write-through (sc1) store and
-// read by one sc1 load: a scalar sc1 store is one fabric write whatever its size, so 8-byte stores cost 2.7x the time per
-// byte of 16-byte ones (MI355X_MICROARCH.md, inter-workgroup visibility table) -- a leader publishes up to 14 x 8 cells
-// per pass.  Each half carries its own tag, so a cell torn between its halves is simply "not ready yet".
-// A block is [slot][16 columns] cells.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr int kCacheSc1 = 16;  // aux bits of the gfx940+ buffer instructions: sc1
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t table_rsrc(const u64 *p, size_t granules) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<u64 *>(p), 0, (int)(granules * sizeof(u64)), 0x00027000);
-}
-__device__ __forceinline__ void put_cell(__amdgpu_buffer_rsrc_t t, unsigned cell, unsigned tag, double v) {
-  const u32x4 d = {(unsigned)__double2loint(v), tag, (unsigned)__double2hiint(v), tag};
-  __builtin_amdgcn_raw_buffer_store_b128(d, t, (int)(cell * 16u), 0, kCacheSc1);
-}
-
 template <int NS, bool MAX = true>
 __device__ __forceinline__ constexpr bool slot_used(int v) { return v < NS || (MAX && v == kSums); }
 
@@ -334,7 +369,8 @@ __device__ __forceinline__ void fold_block(double (&val)[4]) {
   if (MAX && r == (kSums & 3)) val[kSums / 4] = mx;
 }
 
-template <int NS, bool MAX = true, class Ctx>
+// PUBLISHED: this workgroup's row is already on its way (worker_reduce<.., PUB>): start at the gathers; sums[] is written only
+template <int NS, bool MAX = true, bool PUBLISHED = false, class Ctx>
 __device__ __forceinline__ bool control_exchange(const Ctx &ctx, unsigned epoch, double *sums, int *s_abort,
                                                  long long *st_, long long &last_) {
   const int lane = threadIdx.x & (kWave - 1);  // a control wave's lane
@@ -348,8 +384,10 @@ __device__ __forceinline__ bool control_exchange(const Ctx &ctx, unsigned epoch,
   const __amdgpu_buffer_rsrc_t rows = table_rsrc(ctx.rows, kRowsGranules), groups = table_rsrc(ctx.groups, kGroupsGranules);
   const unsigned my_rows = ((epoch & 1u) * kMaxGroups + grp) * kBlockCells;   // first cell of this group's block
   const unsigned my_groups = (epoch & 1u) * kReplicas * kBlockCells;           // first cell of copy 0 of the group rows
-  const bool withhold = (int)epoch == ctx.sabotage_epoch && blockIdx.x == gridDim.x - 1;  // test hook, see ResidentCtx
-  if (slot_used<NS, MAX>(lane) && lane <= kSums && !withhold) put_cell(rows, my_rows + lane * kGroup + blockIdx.x % kGroup, tag, sums[lane]);
+  if constexpr (!PUBLISHED) {
+    const bool withhold = (int)epoch == ctx.sabotage_epoch && blockIdx.x == gridDim.x - 1;  // test hook, see ResidentCtx
+    if (slot_used<NS, MAX>(lane) && lane <= kSums && !withhold) put_cell(rows, my_rows + lane * kGroup + blockIdx.x % kGroup, tag, sums[lane]);
+  }
 
   double val[4];
   unsigned polls = 0;
@@ -707,22 +745,23 @@ __device__ __forceinline__ void sweep_pass(int kind, const PassUniforms<MODEL> &
 
 // the matching reduction (the number of sums depends on the request kind only: wave-uniform; a trial sweep leaves kTrialSums:
 // device_common.h)
-template <int METHOD>
-__device__ __forceinline__ void reduce_pass(int kind, const double *acc, double mx, double *red, double *sums, long long *st_, long long &last_) {
+template <int METHOD, bool PUB = false>
+__device__ __forceinline__ void reduce_pass(int kind, const double *acc, double mx, double *red, double *sums, const RowPublish &pub, long long *st_,
+                                            long long &last_) {
   if constexpr (METHOD == 0) {
     switch (kind) {
-    case RQ_DIF_JAC: worker_reduce<SumLayout<kM>::DIF_JAC, false>(acc, mx, red, sums, st_, last_); break;
-    case RQ_DIF_TRIAL: worker_reduce<kTrialSums, false>(acc, mx, red, sums, st_, last_); break;
-    case RQ_EVAL_MULTI: worker_reduce<kMaxCand, false>(acc, mx, red, sums, st_, last_); break;
-    default: worker_reduce<1, false>(acc, mx, red, sums, st_, last_); break;
+    case RQ_DIF_JAC: worker_reduce<SumLayout<kM>::DIF_JAC, false, PUB>(acc, mx, red, sums, pub, st_, last_); break;
+    case RQ_DIF_TRIAL: worker_reduce<kTrialSums, false, PUB>(acc, mx, red, sums, pub, st_, last_); break;
+    case RQ_EVAL_MULTI: worker_reduce<kMaxCand, false, PUB>(acc, mx, red, sums, pub, st_, last_); break;
+    default: worker_reduce<1, false, PUB>(acc, mx, red, sums, pub, st_, last_); break;
     }
   } else {
     switch (kind) {
     // (max |e| is read after plain evaluations only -- the overflow guards of lmbc_core.c:748, :915 -- so the Jacobian and
     // multi-candidate passes carry no max slot: one reduction value, one exchange cell and one gather instruction less)
-    case RQ_JAC: worker_reduce<SumLayout<kM>::JAC, false>(acc, mx, red, sums, st_, last_); break;
-    case RQ_EVAL_MULTI: worker_reduce<kMaxCand, false>(acc, mx, red, sums, st_, last_); break;
-    default: worker_reduce<1, METHOD == 1>(acc, mx, red, sums, st_, last_); break;  // (dlevmar_der never reads max |e|)
+    case RQ_JAC: worker_reduce<SumLayout<kM>::JAC, false, PUB>(acc, mx, red, sums, pub, st_, last_); break;
+    case RQ_EVAL_MULTI: worker_reduce<kMaxCand, false, PUB>(acc, mx, red, sums, pub, st_, last_); break;
+    default: worker_reduce<1, METHOD == 1, PUB>(acc, mx, red, sums, pub, st_, last_); break;  // (dlevmar_der never reads max |e|)
     }
   }
 }

@@ -137,6 +137,14 @@ RESIDENT_KERNEL_HEAD {
   }
   __syncthreads();  // machine, uniforms, s_bad and the parked samples are visible
 
+  // a single fit over several workgroups: the waves that finish a reduction slot publish its exchange cell (worker_reduce)
+  constexpr bool kPub = !BATCHED;
+  auto row_pub = [&](unsigned epoch) {
+    if constexpr (kPub)
+      return row_publish(ctx, epoch);
+    else
+      return RowPublish{nullptr, 0u, 0u, false, false};
+  };
   int cur_sel_hx = 0, cur_sel_j = 0;
   // what every wave does at the top of a pass (dlevmar_dif): learn what the machine decided about the previous trial
   auto decisions = [&](auto &st, bool &pend) {
@@ -218,7 +226,8 @@ RESIDENT_KERNEL_HEAD {
         }
         RSTAMP(5);  // the control wave's own sweep
         RTRACE(ctx, epoch, 1, wall_clock64());
-        reduce_pass<METHOD>(kind, acc, mx, red, sums, st_, last_);  // X1, X2: sums[] hold this workgroup's partial sums
+        // X1, X2: sums[] hold this workgroup's partial sums -- or, in a fit over several workgroups, X1: its row is published
+        reduce_pass<METHOD, kPub>(kind, acc, mx, red, sums, row_pub(epoch), st_, last_);
       }
       RSTAMP(1);  // reduction + waiting for the slowest wave
       RTRACE(ctx, epoch, 2, wall_clock64());
@@ -238,16 +247,16 @@ RESIDENT_KERNEL_HEAD {
        if (gridDim.x > 1) {      // ... and so is a single fit of <= 4096 samples: no exchange, no visibility hops
         if constexpr (METHOD == 0) {
           switch (kind) {
-          case RQ_DIF_JAC: alive = control_exchange<SumLayout<kM>::DIF_JAC, false>(ctx, epoch, sums, &s_abort, st_, last_); break;
-          case RQ_DIF_TRIAL: alive = control_exchange<kTrialSums, false>(ctx, epoch, sums, &s_abort, st_, last_); break;
-          case RQ_EVAL_MULTI: alive = control_exchange<kMaxCand, false>(ctx, epoch, sums, &s_abort, st_, last_); break;
-          default: alive = control_exchange<1, false>(ctx, epoch, sums, &s_abort, st_, last_); break;
+          case RQ_DIF_JAC: alive = control_exchange<SumLayout<kM>::DIF_JAC, false, kPub>(ctx, epoch, sums, &s_abort, st_, last_); break;
+          case RQ_DIF_TRIAL: alive = control_exchange<kTrialSums, false, kPub>(ctx, epoch, sums, &s_abort, st_, last_); break;
+          case RQ_EVAL_MULTI: alive = control_exchange<kMaxCand, false, kPub>(ctx, epoch, sums, &s_abort, st_, last_); break;
+          default: alive = control_exchange<1, false, kPub>(ctx, epoch, sums, &s_abort, st_, last_); break;
           }
         } else {
           switch (kind) {
-          case RQ_JAC: alive = control_exchange<SumLayout<kM>::JAC, false>(ctx, epoch, sums, &s_abort, st_, last_); break;
-          case RQ_EVAL_MULTI: alive = control_exchange<kMaxCand, false>(ctx, epoch, sums, &s_abort, st_, last_); break;
-          default: alive = control_exchange<1, METHOD == 1>(ctx, epoch, sums, &s_abort, st_, last_); break;
+          case RQ_JAC: alive = control_exchange<SumLayout<kM>::JAC, false, kPub>(ctx, epoch, sums, &s_abort, st_, last_); break;
+          case RQ_EVAL_MULTI: alive = control_exchange<kMaxCand, false, kPub>(ctx, epoch, sums, &s_abort, st_, last_); break;
+          default: alive = control_exchange<1, METHOD == 1, kPub>(ctx, epoch, sums, &s_abort, st_, last_); break;
           }
         }
        }
@@ -257,12 +266,16 @@ RESIDENT_KERNEL_HEAD {
         return;
       }
       bool stepped = false;
+      constexpr bool kTrialFromRegs = METHOD == 0 && !BATCHED;  // (the batched kernels keep su.build)
+      typename std::conditional<METHOD == 0, typename DifMachine<kM>::NextTrial, int>::type next_trial{};  // what a fused step issued (its locals)
+      (void)next_trial;
       if (kind == RQ_DIF_TRIAL) {
         if constexpr (METHOD == 0) {
           // trial judged -> next trial, most steps of a fit: one straight-line block on registers (lm_machine.h:
           // fused_trial_step; nothing of it is live outside this block).  Declined: the machine and sums[] are untouched.
           if (fused) {
-            stepped = fused_trial_step_device<Machine>(cold0, ints_regs, static_cast<typename Machine::CoreReals &>(sm.h), sm.h.cool, sm.h.req, sums, su.dp);
+            stepped = fused_trial_step_device<Machine>(cold0, ints_regs, static_cast<typename Machine::CoreReals &>(sm.h), sm.h.cool, sm.h.req, sums, su.dp,
+                                                       kTrialFromRegs ? &next_trial : nullptr);
             if (stepped) {
               ++n_fused;
               Machine::uniform_ints(ints_regs);
@@ -296,7 +309,10 @@ RESIDENT_KERNEL_HEAD {
           sm.template step<true>(sums, sums[kSums]);
       }
       RSTAMP(7);  // the step alone
-      if (sm.h.req.kind != RQ_DONE) {
+      if (kTrialFromRegs && stepped) {
+        // the fused step issued a plain trial: its uniforms from the step's registers, nothing read back behind its stores
+        if constexpr (METHOD == 0) su.build_trial(next_trial.q, next_trial.dp, next_trial.dp_l2, false);
+      } else if (sm.h.req.kind != RQ_DONE) {
         // (lane-parallel for the single box-constrained fit only: the dif kernels have no register for it -- 5 -> 10 spilled VGPRs --
         // and hardly a request that gains; the batched bc kernel spills 8 with it)
         if constexpr (METHOD == 1 && !BATCHED)
@@ -349,10 +365,7 @@ RESIDENT_KERNEL_HEAD {
 
   // ============================= waves 1..7: register-resident samples ===========================================
   long long wst_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, wlast_ = 0;  // (stamps are the control wave's; these are never read)
-#ifdef BRDF_TRACE_WORKERS
-  unsigned wepoch = 0;
-#endif
-  for (;;) {
+  for (unsigned epoch = 0;; ++epoch) {  // (the waves loop in lockstep with the control wave: its epoch)
     const int kind = sm.h.req.kind;
     if (kind == RQ_DONE) break;
     bool pend;
@@ -365,12 +378,11 @@ RESIDENT_KERNEL_HEAD {
     sweep_pass<MODEL, METHOD, FAST>(kind, su, rs, jl, tid, nk, nfull, okm, pend, dpp, acc, mx);
 #ifdef BRDF_TRACE_WORKERS  // (diagnostic: when do the register-resident waves finish their sweeps? slots 6, 7 = waves 4, 7)
     if constexpr (!BATCHED) {
-      if (wave == 4) RTRACE(ctx, wepoch, 6, wall_clock64());
-      if (wave == 7) RTRACE(ctx, wepoch, 7, wall_clock64());
-      ++wepoch;
+      if (wave == 4) RTRACE(ctx, epoch, 6, wall_clock64());
+      if (wave == 7) RTRACE(ctx, epoch, 7, wall_clock64());
     }
 #endif
-    reduce_pass<METHOD>(kind, acc, mx, red, sums, wst_, wlast_);
+    reduce_pass<METHOD, kPub>(kind, acc, mx, red, sums, row_pub(epoch), wst_, wlast_);
     __syncthreads();  // B: the control wave has stepped the machine
     if (s_abort) return;
   }
