@@ -216,6 +216,17 @@ __device__ __forceinline__ bool fused_trial_step_device(const typename Machine::
   return Machine::template fused_trial_step<true, true>(c, hi, h, cool, req, out, next);
 }
 
+// The same step in its two stages (DifMachine::fused_trial_step_split): `between(tc)` runs behind the first stage's stores --
+// what other waves read before the next exchange -- and in front of the second's.
+template <class Machine, class Between>
+__device__ __forceinline__ bool fused_trial_step_split_device(const typename Machine::Cold &c, typename Machine::CoreInts &hi, typename Machine::CoreReals &h,
+                                                              typename Machine::Cool &cool, Request<kM> &req, const double *sums, const double *dpv,
+                                                              Between &&between) {
+  if (hi.phase != Machine::D_AFTER_TRIAL) return false;
+  double out[SumLayout<kM>::DIF_TRIAL];
+  expand_trial_sums_to(h, cool, dpv, sums, out);
+  return Machine::template fused_trial_step_split<true, true>(c, hi, h, cool, req, out, between);
+}
 
 // number of sum slots a request kind produces
 __host__ __device__ __forceinline__ int slots_of(int kind) {

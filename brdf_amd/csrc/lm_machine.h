@@ -484,9 +484,29 @@ struct DifMachine {
   struct NextTrial {
     Real q[M], dp[M], dp_l2;
   };
-  template <bool ONE_LANE = false, bool MULTI = false>
-  static LM_HD bool fused_trial_step(const Cold &c, CoreInts &hi, CoreReals &h, Cool &cool, Request<M, Real> &req, const Real *s,
-                                     NextTrial *next = nullptr) {
+  // The step in two stages, for a kernel whose other waves wait at a barrier for the next request while this one stores:
+  //   first stage    every test and all arithmetic.  Taken: stores what ANOTHER wave reads before the next exchange, and the
+  //                  counters (scalar registers in that kernel); the rest of the new state stays in locals (`tc`).
+  //   between(tc)    the caller's: the next pass's uniforms from tc, its barrier.  Runs only when the step is taken.
+  //   second stage   fused_trial_commit stores the rest from tc.  Nothing but the stepping wave itself reads it, one exchange later.
+  // (One function with the caller's part handed in, not two calls: behind a first stage that RETURNS, the second hangs off a
+  // merge of all its ways out, and hipcc spilled the whole of tc to scratch around it -- 7 -> 126 spilled VGPRs.)
+  // The early fields -- fixed from what the waves of resident_fit_kernel.inc read at the top of a pass (the loop's
+  // `req.kind`, decisions(): req.kind, req.sel_j, req.sel_hx; sweep_pass reads the uniforms and dp_prev[], never the machine):
+  //     CoreInts (all of it), req.kind, req.sel_hx, req.sel_j
+  // The late fields -- everything else the step writes:
+  //     CoreReals (all of it), Cool: diag, pdp, spec_jtj, spec_jte, Request: central, aux, dp_l2, scal, nk, p, d, q, dp
+  // (Cool::init_e2, Cool::ml2 and Request::pk are not written by this step at all.)  fused_trial_commit does not store the
+  // early fields again: in that kernel the other waves are reading them by then.
+  // tests/cpp/split_commit_harness.cpp checks the state between the stages and behind them against the one-shot step.
+  struct TrialCommit {
+    Real mu, p_e2, jte_inf, p_l2, dp_l2, pdp_e2;
+    Real jtj[M * M], spec_jtj[M * M];
+    Real p[M], jte[M], dp[M], diag[M], pdp[M];
+  };
+  template <bool ONE_LANE = false, bool MULTI = false, class Between>
+  static LM_HD bool fused_trial_step_split(const Cold &c, CoreInts &hi, CoreReals &h, Cool &cool, Request<M, Real> &req, const Real *s,
+                                           Between &&between) {
     constexpr int NL = SumLayout<M>::NL;
     if (hi.phase != D_AFTER_TRIAL || !c.speculative || hi.stop) return false;
     // ---- D_AFTER_TRIAL
@@ -556,14 +576,8 @@ struct DifMachine {
     ok = (ok && !(dp_l2 <= c.o.eps2sq * p_l2) && !(dp_l2 >= (p_l2 + c.o.eps2) / (Real(kEpsilon) * Real(kEpsilon)))) ? 1 : 0;
     if (ONE_LANE) ok = lm_uniform(ok);
     if (!ok) return false;
-    // ---- every test has passed: commit
-    if (next) {
-      for (int i = 0; i < M; ++i) {
-        next->q[i] = pdpn[i];
-        next->dp[i] = dpn[i];
-      }
-      next->dp_l2 = dp_l2;
-    }
+    // ---- every test has passed: the early fields, and the rest into tc
+    TrialCommit tc;
     hi.k = k1;
     hi.nu = nu;
     ++hi.nfev;
@@ -575,33 +589,75 @@ struct DifMachine {
     hi.sel_j ^= 1;
     hi.accepted = acc;
     if (MULTI) hi.chain = hi.single = 0;
-    h.mu = mu;
-    h.p_e2 = pe2n;
-    h.jte_inf = jte_inf;
-    h.p_l2 = p_l2;
-    h.dp_l2 = dp_l2;
-    h.pdp_e2 = e2;
-    for (int i = 0; i < M * M; ++i) {
-      h.jtj[i] = Am[i];
-      cool.spec_jtj[i] = A[i];
-    }
-    for (int i = 0; i < M; ++i) {
-      h.p[i] = pn[i];
-      h.jte[i] = b[i];
-      h.dp[i] = dpn[i];
-      cool.diag[i] = diag[i];
-      cool.pdp[i] = pdpn[i];
-      cool.spec_jte[i] = b[i];
-    }
-    clear_req(hi, req);
     req.kind = RQ_DIF_TRIAL;
-    for (int i = 0; i < M; ++i) {
-      req.p[i] = pn[i];
-      req.q[i] = pdpn[i];
-      req.dp[i] = dpn[i];
+    req.sel_hx = hi.sel_hx;
+    req.sel_j = hi.sel_j;
+    tc.mu = mu;
+    tc.p_e2 = pe2n;
+    tc.jte_inf = jte_inf;
+    tc.p_l2 = p_l2;
+    tc.dp_l2 = dp_l2;
+    tc.pdp_e2 = e2;
+    for (int i = 0; i < M * M; ++i) {
+      tc.jtj[i] = Am[i];
+      tc.spec_jtj[i] = A[i];
     }
-    req.dp_l2 = dp_l2;
+    for (int i = 0; i < M; ++i) {
+      tc.p[i] = pn[i];
+      tc.jte[i] = b[i];
+      tc.dp[i] = dpn[i];
+      tc.diag[i] = diag[i];
+      tc.pdp[i] = pdpn[i];
+    }
+    between(static_cast<const TrialCommit &>(tc));
+    fused_trial_commit(h, cool, req, tc);
     return true;
+  }
+  static LM_HD void fused_trial_commit(CoreReals &h, Cool &cool, Request<M, Real> &req, const TrialCommit &tc) {
+    h.mu = tc.mu;
+    h.p_e2 = tc.p_e2;
+    h.jte_inf = tc.jte_inf;
+    h.p_l2 = tc.p_l2;
+    h.dp_l2 = tc.dp_l2;
+    h.pdp_e2 = tc.pdp_e2;
+    for (int i = 0; i < M * M; ++i) {
+      h.jtj[i] = tc.jtj[i];
+      cool.spec_jtj[i] = tc.spec_jtj[i];
+    }
+    for (int i = 0; i < M; ++i) {
+      h.p[i] = tc.p[i];
+      h.jte[i] = tc.jte[i];
+      h.dp[i] = tc.dp[i];
+      cool.diag[i] = tc.diag[i];
+      cool.pdp[i] = tc.pdp[i];
+      cool.spec_jte[i] = tc.jte[i];
+    }
+    // (clear_req's stores, without the three early fields)
+    req.central = 0;
+    req.aux = 0;
+    req.scal = Real(1.0);
+    req.nk = 0;
+    for (int i = 0; i < M; ++i) {
+      req.p[i] = tc.p[i];
+      req.d[i] = Real(0.0);
+      req.q[i] = tc.pdp[i];
+      req.dp[i] = tc.dp[i];
+    }
+    req.dp_l2 = tc.dp_l2;
+  }
+  // the one-shot form: both stages back to back
+  template <bool ONE_LANE = false, bool MULTI = false>
+  static LM_HD bool fused_trial_step(const Cold &c, CoreInts &hi, CoreReals &h, Cool &cool, Request<M, Real> &req, const Real *s,
+                                     NextTrial *next = nullptr) {
+    return fused_trial_step_split<ONE_LANE, MULTI>(c, hi, h, cool, req, s, [next](const TrialCommit &tc) {
+      if (next) {
+        for (int i = 0; i < M; ++i) {
+          next->q[i] = tc.pdp[i];
+          next->dp[i] = tc.dp[i];
+        }
+        next->dp_l2 = tc.dp_l2;
+      }
+    });
   }
 
   // ONE_LANE: the caller guarantees that exactly one lane of the wave executes this step (see lm_uniform)

@@ -267,18 +267,38 @@ RESIDENT_KERNEL_HEAD {
       }
       bool stepped = false;
       constexpr bool kTrialFromRegs = METHOD == 0 && !BATCHED;  // (the batched kernels keep su.build)
-      typename std::conditional<METHOD == 0, typename DifMachine<kM>::NextTrial, int>::type next_trial{};  // what a fused step issued (its locals)
-      (void)next_trial;
       if (kind == RQ_DIF_TRIAL) {
         if constexpr (METHOD == 0) {
           // trial judged -> next trial, most steps of a fit: one straight-line block on registers (lm_machine.h:
           // fused_trial_step; nothing of it is live outside this block).  Declined: the machine and sums[] are untouched.
           if (fused) {
-            stepped = fused_trial_step_device<Machine>(cold0, ints_regs, static_cast<typename Machine::CoreReals &>(sm.h), sm.h.cool, sm.h.req, sums, su.dp,
-                                                       kTrialFromRegs ? &next_trial : nullptr);
-            if (stepped) {
-              ++n_fused;
-              Machine::uniform_ints(ints_regs);
+            if constexpr (kTrialFromRegs) {
+              // A single fit runs the step in its two stages.  The first stores what the other waves read at the top of the next
+              // pass (lm_machine.h lists the fields).  Between the stages: the next trial's uniforms from the step's registers,
+              // nothing read back, and barrier B.  Behind it, while the other seven waves sweep, the second stage stores the rest
+              // of the machine's new state (~30 ds_writes nobody but this wave reads, one exchange away: expand_trial_sums_to).
+              const bool took = fused_trial_step_split_device<Machine>(
+                  cold0, ints_regs, static_cast<typename Machine::CoreReals &>(sm.h), sm.h.cool, sm.h.req, sums, su.dp, [&](const typename Machine::TrialCommit &late) {
+#pragma unroll
+                    for (int j = 0; j < kM; ++j) dp_prev[j] = su.dp[j];
+                    dp_prev[kM] = su.dp_l2;
+                    RSTAMP(7);  // the step alone
+                    su.build_trial(late.pdp, late.dp, late.dp_l2, false);
+                    RTRACE(ctx, epoch, 5, wall_clock64());
+                    __syncthreads();  // B: the next request and its uniforms are in LDS
+                    RSTAMP(4);
+                  });
+              if (took) {  // (the pass has ended in there)
+                ++n_fused;
+                Machine::uniform_ints(ints_regs);
+                continue;
+              }
+            } else {
+              stepped = fused_trial_step_device<Machine>(cold0, ints_regs, static_cast<typename Machine::CoreReals &>(sm.h), sm.h.cool, sm.h.req, sums, su.dp);
+              if (stepped) {
+                ++n_fused;
+                Machine::uniform_ints(ints_regs);
+              }
             }
           }
           if (!stepped) expand_trial_sums(static_cast<const typename Machine::Core &>(sm.h), sm.h.cool, su.dp, sums);
@@ -309,10 +329,7 @@ RESIDENT_KERNEL_HEAD {
           sm.template step<true>(sums, sums[kSums]);
       }
       RSTAMP(7);  // the step alone
-      if (kTrialFromRegs && stepped) {
-        // the fused step issued a plain trial: its uniforms from the step's registers, nothing read back behind its stores
-        if constexpr (METHOD == 0) su.build_trial(next_trial.q, next_trial.dp, next_trial.dp_l2, false);
-      } else if (sm.h.req.kind != RQ_DONE) {
+      if (sm.h.req.kind != RQ_DONE) {
         // (lane-parallel for the single box-constrained fit only: the dif kernels have no register for it -- 5 -> 10 spilled VGPRs --
         // and hardly a request that gains; the batched bc kernel spills 8 with it)
         if constexpr (METHOD == 1 && !BATCHED)
