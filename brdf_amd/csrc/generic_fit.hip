@@ -16,6 +16,8 @@
 // J^T J, with the reference's n*m <= 1024 / < 1024 switch): results are then bit-identical to levmar's, which
 // is what lets the reference's own known answers (lmdemo.c) be replayed through this ABI.
 // Larger problems use a deterministic workgroup tree (one workgroup; the callback dominates there anyway).
+// With dscl the Jacobian passes scale J <- J*D element by element before the sums, as lmbc_core.c:562-569 does (BcMachine's
+// has_dscl = 2), so that the bit-for-bit replay holds for scales that are no powers of two.
 #include <cstdio>
 #include <cstring>
 #include <type_traits>
@@ -39,8 +41,8 @@ struct GenArgs {
   Real *hx_rw;      // writable alias of hx (accept: hx <- wrk)
   Real *jac;        // n x m row-major, as levmar stores it (jac[i*m + j])
   Real *out;        // kGenSums doubles
-  int n, m, kind, central, exact, accepted, bc_rule, store_hx, user_jac;
-  Real dinv[kGenMaxM], dp[kGenMaxM], dp_l2, scal;
+  int n, m, kind, central, exact, accepted, bc_rule, store_hx, user_jac, scale_jac;
+  Real dinv[kGenMaxM], dp[kGenMaxM], dscl[kGenMaxM], dp_l2, scal;
 };
 
 // ---- exact (reference-order) single-lane routines ---------------------------------------------------------
@@ -136,8 +138,12 @@ __global__ __launch_bounds__(kGenThreads) void gen_pass_kernel(GenArgs<Real> a) 
       for (int j = 0; j < m; ++j) {
         const Real v = a.central ? (a.aux[(size_t)(2 * j + 1) * n + i] - a.aux[(size_t)(2 * j) * n + i])
                                    : (a.aux[(size_t)j * n + i] - a.hx[i]);
-        a.jac[(size_t)i * m + j] = v * a.dinv[j];
+        const Real d = v * a.dinv[j];
+        a.jac[(size_t)i * m + j] = a.scale_jac ? d * a.dscl[j] : d;  // J <- J*D, lmbc_core.c:562-569
       }
+  } else if (a.kind == RQ_JAC && a.scale_jac) {  // the caller's Jacobian: J <- J*D
+    for (int i = tid; i < n; i += kGenThreads)
+      for (int j = 0; j < m; ++j) a.jac[(size_t)i * m + j] *= a.dscl[j];
   } else if (a.kind == RQ_DIF_UPDATE) {  // lm_core.c:760-766
     for (int i = tid; i < n; i += kGenThreads) {
       Real *row = a.jac + (size_t)i * m;
@@ -240,7 +246,12 @@ int generic_run(user_func_of<Real> func, user_jacf_of<Real> jacf, Real *p, Real 
     mach.start(p, n, lb, ub, dscl, itmax, opts, covar != nullptr);
   else
     mach.start(p, n, itmax, opts, covar != nullptr);
-  if constexpr (METHOD == 1) mach.c.analytic_jac = jacf ? 1 : 0;
+  if constexpr (METHOD == 1) {
+    mach.c.analytic_jac = jacf ? 1 : 0;
+    // the Jacobian passes below scale J by dscl before they form J^T J and J^T e, as the reference does (lmbc_core.c:562-569):
+    // folded into the reduced products instead, the last bits differ whenever a scale is no power of two
+    if (mach.c.has_dscl) mach.c.has_dscl = 2;
+  }
   if (mach.h.req.kind == RQ_DONE) {
     int bad = 1;
     if constexpr (METHOD == 1) bad = mach.c.bad_input;
@@ -296,6 +307,11 @@ int generic_run(user_func_of<Real> func, user_jacf_of<Real> jacf, Real *p, Real 
     a.scal = r.scal;
     a.dp_l2 = r.dp_l2;
     for (int j = 0; j < M; ++j) a.dp[j] = r.dp[j];
+    if constexpr (METHOD == 1)
+      if (mach.c.has_dscl && r.kind == RQ_JAC) {
+        a.scale_jac = 1;
+        for (int j = 0; j < M; ++j) a.dscl[j] = mach.c.dscl[j];
+      }
     Real pt[M];
     size_t planes = 0;
     switch (r.kind) {

@@ -1032,7 +1032,7 @@ struct BcMachine {
   struct Cold {  // configuration + results (see DifMachine for the Hot/Cold rationale)
     FitOptionsT<Real> o;
     int itmax, n, want_covar;
-    int has_lb, has_ub, has_dscl;
+    int has_lb, has_ub, has_dscl;  // has_dscl: 0 none; 1 folded into the reduced J^T J, J^T e; 2 the pass scales J itself
     Real lb[M], ub[M], dscl[M];
     int infeasible_mask, bad_input;
     int bad_config;    // configure(): 0, or the argument check that failed (becomes bad_input of every fit begun)
@@ -1308,7 +1308,8 @@ struct BcMachine {
         if (SPECJ) h.spec_state = 0;
         unpack_lower<M>(sv, h.jtj);
         for (int i = 0; i < M; ++i) h.jte[i] = sv[SumLayout<M>::NL + i];
-        if (c.has_dscl) {  // J <- J*D (lmbc_core.c:562-569) folded into the reduced products
+        if (c.has_dscl == 1) {  // J <- J*D (lmbc_core.c:562-569) folded into the reduced products (has_dscl == 2: the pass scaled J
+                                // itself before it formed them, as the reference does -- generic_fit.hip, bit for bit)
           for (int i = 0; i < M; ++i) {
             h.jte[i] *= c.dscl[i];
             for (int j = 0; j < M; ++j) h.jtj[i * M + j] *= c.dscl[i] * c.dscl[j];

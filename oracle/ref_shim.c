@@ -177,3 +177,6 @@ void wide_cheb_jac(double *p, double *jac, int m, int n, void *d)
     }
   }
 }
+
+/* the same problem for float callbacks (sp_wide_cheb / sp_wide_cheb_jac: the same text with float, sinf, cosf) */
+#include "sp_wide_cheb.c"
