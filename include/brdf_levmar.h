@@ -61,7 +61,10 @@ enum { BRDF_METHOD_DIF = 0, BRDF_METHOD_BC_DIF = 1,
  *     library's device code, m must be 3 (x == NULL means a zero measurement vector, as in levmar).
  *   - any other `func`, 1 <= m <= 8: `func` is called on the host (it is the caller's code), all n-sized work
  *     around it runs on the device; small problems (n*m <= 65536) are summed in the reference's order and
- *     reproduce levmar bit for bit. */
+ *     reproduce levmar bit for bit.
+ *   - `covar` (this entry and the three below, for a registered model): where levmar leaves it unwritten or writes memory it
+ *     never set -- itmax = 0, a stop before the first Jacobian (info[8] == 0), a singular J^T J ("singular matrix") -- the
+ *     nine values returned are 0.0.  A refused call (n < m, a lower bound above its upper one) does not touch it. */
 int dlevmar_dif(void (*func)(double *p, double *hx, int m, int n, void *adata), double *p, double *x,
                 int m, int n, int itmax, double *opts, double *info, double *work, double *covar,
                 void *adata);

@@ -177,6 +177,7 @@ static int lu_factor(double *a, int *perm, double *scale, int m)
         pivot = i;
       }
     }
+    if (pivot < 0) return 0; /* a first column of NaN (a J'J the caller never formed): the reference exchanges row -1 there */
     if (j != pivot) {
       for (k = 0; k < m; ++k) {
         const double t = a[pivot * m + k];
@@ -1086,18 +1087,24 @@ int orc_dlevmar_bc_dif(orc_func_t f, double *p, double *x, int m, int n, double 
   return ret;
 }
 
-int orc_brdf_fit(int method, int model, double *angles, double *x, int n, double *p, int itmax,
-                 double *opts, double *lb, double *ub, double *info)
+int orc_brdf_fit_covar(int method, int model, double *angles, double *x, int n, double *p, int itmax,
+                       double *opts, double *lb, double *ub, double *dscl, double *info, double *covar)
 {
   struct orc_extra_data d;
   d.angles = angles;
   d.modelInfo = model;
-  if (method == 0) return orc_dlevmar_dif(orc_brdf_func, p, x, 3, n, itmax, opts, info, NULL, NULL, &d);
+  if (method == 0) return orc_dlevmar_dif(orc_brdf_func, p, x, 3, n, itmax, opts, info, NULL, covar, &d);
   if (method == 3) /* dlevmar_der with the analytic Jacobian */
-    return orc_dlevmar_der(orc_brdf_func, orc_brdf_jac, p, x, 3, n, itmax, opts, info, NULL, NULL, &d);
+    return orc_dlevmar_der(orc_brdf_func, orc_brdf_jac, p, x, 3, n, itmax, opts, info, NULL, covar, &d);
   if (method == 2) /* dlevmar_bc_der with the analytic Jacobian */
-    return orc_dlevmar_bc_der(orc_brdf_func, orc_brdf_jac, p, x, 3, n, lb, ub, NULL, itmax, opts, info, NULL, NULL, &d);
-  return orc_dlevmar_bc_dif(orc_brdf_func, p, x, 3, n, lb, ub, NULL, itmax, opts, info, NULL, NULL, &d);
+    return orc_dlevmar_bc_der(orc_brdf_func, orc_brdf_jac, p, x, 3, n, lb, ub, dscl, itmax, opts, info, NULL, covar, &d);
+  return orc_dlevmar_bc_dif(orc_brdf_func, p, x, 3, n, lb, ub, dscl, itmax, opts, info, NULL, covar, &d);
+}
+
+int orc_brdf_fit(int method, int model, double *angles, double *x, int n, double *p, int itmax,
+                 double *opts, double *lb, double *ub, double *info)
+{
+  return orc_brdf_fit_covar(method, model, angles, x, n, p, itmax, opts, lb, ub, NULL, info, NULL);
 }
 
 /* S independent fits one after the other -- the shape of CalcBRDFEquation's pixel loop (brdfdata.cpp:1195-1220):

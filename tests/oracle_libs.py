@@ -49,6 +49,28 @@ def brdf_fit(which: str, method: int, model: int, angles, x, p0, itmax=100, opts
     return r, p, info
 
 
+def brdf_fit_covar(which: str, method: int, model: int, angles, x, p0, itmax=100, opts=None, lb=None, ub=None, dscl=None):
+    """brdf_fit with a covar array (pre-filled with NaN, so that "never written" shows) and, for the box methods, dscl: the oracle
+    ('orc') or the host-driven machines ('hm', 'hm_fast').  Returns (ret, p[3], info[10], covar[3,3])."""
+    a = f64(angles)
+    xx = f64(x)
+    n = xx.size
+    p = f64(p0).copy()
+    info = np.zeros(10)
+    covar = np.full(9, np.nan)
+    bc = method in (1, 2)
+    o = f64(opts)
+    l, u, d = ((None if v is None else f64(v).copy()) if bc else None for v in (lb, ub, dscl))  # (copies: the reference scales the box in place)
+    if which == "orc":
+        r = orc.orc_brdf_fit_covar(method, model, ptr(a), ptr(xx), n, ptr(p), itmax, ptr(o), ptr(l), ptr(u), ptr(d), ptr(info), ptr(covar))
+    elif which in ("hm", "hm_fast"):
+        fn = hm.hm_brdf_fit if which == "hm" else hm.hm_brdf_fit_fast
+        r = fn(method, model, ptr(a), ptr(xx), n, ptr(p), itmax, ptr(o), ptr(l), ptr(u), ptr(d), ptr(info), ptr(covar), None)
+    else:
+        raise ValueError(which)
+    return r, p, info, covar.reshape(3, 3)
+
+
 def model_values(model: int, angles, p):
     a = f64(angles)
     n = a.size // 3

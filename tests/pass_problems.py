@@ -6,7 +6,7 @@ drops a sample or a damping update off by a factor -- by another path.  So a fit
 loosened stop rule, by itmax = 0 -- and everything it returns is compared with the oracle: ret, p, info[0..4] within the case's
 tolerance, info[5..9] (iterations, reason, nfev, njev, nlss) exactly.
 
-A case is (problem, method, itmax, opts).  yardstick(case) says how tightly the oracle alone determines its result: the oracle
+A case is (problem, method, itmax, opts[, dscl]).  yardstick(case) says how tightly the oracle alone determines its result: the oracle
 is run once as it is, on four seeded permutations of the samples (the difference a tree sum makes) and four times with every
 model value -- and, for the analytic methods, every Jacobian entry -- multiplied by 1 + k * 2^-53, k uniform in [-K, K] per
 value and per call, K = 8 (the bound test_model_values_match_oracle holds the device's model values to) plus |p2 * log c| for
@@ -22,6 +22,15 @@ Where the reference never forms a Jacobian (info[8] == 0: itmax = 0, or a stop a
 info[4] from memory it never wrote; these two are not compared there.  At itmax = 0 only ret = 0, p == p0, info[0] == info[1],
 info[5..9] = 0, 3, 1, 0, 0 are defined.
 
+The covariance (results that carry one: the single-fit entries) is one more field, `covar`: the difference is max over i, j of
+|C_ij - C_ref_ij| / sqrt(C_ref_ii * C_ref_jj), the tolerance 8 x the spread of the eight re-runs with the same floor.  It is compared
+where the case is stable (a converged case: where all nine runs end with reason 1 or 2), all nine covariances are finite with a
+positive diagonal and the tolerance is <= 1e-6 (an n for n - 3 at n = 262145 is 1.1e-5, a missing dscl factor or a damped diagonal
+is percent-sized).  Where the reference writes nothing defined -- itmax = 0, info[8] == 0, a J'J that orc_covar finds singular (the
+NaN the array was filled with survives) -- the product returns nine zeros, and that is asserted.  At most 10 % of a test's
+covariances may be left out and no cell with none judged.  A case may carry dscl (the box methods).  Converged cases
+(converged_cases: synth.ITMAX, synth.OPTS) change their counts from run to run: only ret >= 0, p, info[1] and covar are judged.
+
 Measured with the oracle alone (tests/test_oracle_passes.py prints them): cases compared / uncompared, and the largest tolerance
 (8 x spread) among the compared ones
 
@@ -30,6 +39,12 @@ Measured with the oracle alone (tests/test_oracle_passes.py prints them): cases 
     options           184      8 (4.2 %)  8.7e-09  1.6e-14  9.2e-09  5.0e-07  1.4e-07  1.8e-07
     stop rules        267     14 (5.0 %)  1.0e-08  1.8e-14  9.7e-09  6.3e-07  5.9e-07  2.1e-07
     itmax = 0          12      0          (defined fields only)
+
+    covar: judged  left out     largest tolerance     |  list               judged  left out    largest tolerance
+    first passes      374     40 (9.7 %)  6.2e-07     |  diagonal scaling       36      0          6.8e-10
+    options           176     16 (8.3 %)  1.3e-07     |  converged fits         22      2 (8.3 %)  2.8e-08
+    stop rules        264     17 (6.0 %)  3.0e-07     |  single fits, n = 5000 256      2 (0.8 %)  8.2e-09
+    itmax = 0          12      0          (nine zeros)|  channels               72      0          3.0e-10
 
 With 8 units of model-value noise the uncompared cases are nearly all dlevmar_bc_dif (and dlevmar_dif at n = 16): its forward
 difference with step 1e-6 turns 8 * 2^-53 on a model value into 1e-9 on a Jacobian entry, and 8 x that is the cap.  The
@@ -61,8 +76,10 @@ METHOD = ("dif", "bc_dif", "bc_der", "der")
 FIELDS = ("p", "info0", "info1", "info2", "info3", "info4")
 BOX_FAMILIES = ("tight_box", "high_lb", "start_on_bound", "diffuse_only", "shiny_beyond_box", "ward_mirror")
 
-Case = collections.namedtuple("Case", "problem method itmax opts")
-Yard = collections.namedtuple("Yard", "ret p info stable spread tol comparable")
+Case = collections.namedtuple("Case", "problem method itmax opts dscl", defaults=(None,))  # dscl: the box methods' diagonal scaling
+# covar: the oracle's 3x3 (NaN where it wrote nothing); covar_rule: "compare", "zeros" (the reference writes nothing defined: the
+# product's nine values are 0.0) or "left out"; settled: all nine runs end with reason 1 or 2 (converged_cases)
+Yard = collections.namedtuple("Yard", "ret p info stable spread tol comparable covar covar_rule settled")
 
 
 def _with(i, v):
@@ -82,7 +99,7 @@ STOPS = {"eps1=1e-2": _with(1, 1e-2), "eps1=1e-1": _with(1, 1e-1), "eps2=1e-2": 
 def problem(key):
     """key -> (angles[3,n], x[n], p0[3], lb[3], ub[3]).  ("single", model, n): synth.make_single; ("surfel", model, n, s): surfel s
     of synth.make_surfels; ("near", model, n, s): the surfel's planes with measurements at the model's start point plus its noise
-    (a fit that is over before it starts); ("channel", model, CHANNEL_N, c): channel_problem; (family, model, n, idx): tests/edge_problems.py.  Box: synth.bounds(model)."""
+    (a fit that is over before it starts); ("zero_ks", model, n): make_single started with ks = 0; ("channel", model, CHANNEL_N, c): channel_problem; (family, model, n, idx): tests/edge_problems.py.  Box: synth.bounds(model)."""
     kind, model, n = key[:3]
     if kind in E.FAMILIES:
         out = E.make(kind, model, n, key[3])
@@ -91,8 +108,10 @@ def problem(key):
     else:
         lb, ub = (np.array(b, dtype=np.float64) for b in synth.bounds(model))
         p0 = np.array(synth.P0[model], dtype=np.float64)
-        if kind == "single":
+        if kind in ("single", "zero_ks"):
             angles, x, _ = synth.make_single(model, n)
+            if kind == "zero_ks":
+                p0[1] = 0.0
         else:
             a, xs, _ = synth.make_surfels(model, n, first=key[3], count=1)
             angles, x = a[0], xs[0]
@@ -112,6 +131,11 @@ def box(case):
     return (lb, ub) if case.method in (1, 2) else (None, None)
 
 
+def scaling(case):
+    """dscl the case's method takes: the case's for dlevmar_bc_dif / bc_der, none otherwise"""
+    return case.dscl if case.method in (1, 2) else None
+
+
 # ---- the oracle, as it is and disturbed -------------------------------------------------------------------------------
 class _Extra(C.Structure):
     _fields_ = [("angles", L.D), ("modelInfo", C.c_int)]
@@ -120,7 +144,7 @@ class _Extra(C.Structure):
 _FUNC = C.CFUNCTYPE(None, L.D, L.D, C.c_int, C.c_int, C.c_void_p)
 
 
-def _noisy_fit(method, model, angles, x, p0, itmax, opts, lb, ub, rng):
+def _noisy_fit(method, model, angles, x, p0, itmax, opts, lb, ub, rng, dscl=None):
     """the oracle's entry point of `method` with callbacks that wrap orc_brdf_func / orc_brdf_jac: every value they return is
     multiplied by 1 + k * 2^-53, |k| <= OWN_UNITS (+ |p2 log c| for Phong / Blinn-Phong)"""
     a = L.f64(angles)
@@ -147,17 +171,19 @@ def _noisy_fit(method, model, angles, x, p0, itmax, opts, lb, ub, rng):
 
     p = L.f64(p0).copy()
     info = np.zeros(10)
-    o, l, u = L.f64(opts), L.f64(lb), L.f64(ub)
-    f, jf = C.cast(func, C.c_void_p), C.cast(jacf, C.c_void_p)
+    covar = np.full(9, np.nan)  # (NaN: "never written" shows)
+    o = L.f64(opts)
+    l, u, d = (None if v is None else L.f64(v).copy() for v in (lb, ub, dscl))  # (copies: the reference scales the box in place)
+    f, jf, cv = C.cast(func, C.c_void_p), C.cast(jacf, C.c_void_p), L.ptr(covar)
     if method == 0:
-        r = L.orc.orc_dlevmar_dif(f, L.ptr(p), L.ptr(xx), 3, n, itmax, L.ptr(o), L.ptr(info), None, None, None)
+        r = L.orc.orc_dlevmar_dif(f, L.ptr(p), L.ptr(xx), 3, n, itmax, L.ptr(o), L.ptr(info), None, cv, None)
     elif method == 3:
-        r = L.orc.orc_dlevmar_der(f, jf, L.ptr(p), L.ptr(xx), 3, n, itmax, L.ptr(o), L.ptr(info), None, None, None)
+        r = L.orc.orc_dlevmar_der(f, jf, L.ptr(p), L.ptr(xx), 3, n, itmax, L.ptr(o), L.ptr(info), None, cv, None)
     elif method == 2:
-        r = L.orc.orc_dlevmar_bc_der(f, jf, L.ptr(p), L.ptr(xx), 3, n, L.ptr(l), L.ptr(u), None, itmax, L.ptr(o), L.ptr(info), None, None, None)
+        r = L.orc.orc_dlevmar_bc_der(f, jf, L.ptr(p), L.ptr(xx), 3, n, L.ptr(l), L.ptr(u), L.ptr(d), itmax, L.ptr(o), L.ptr(info), None, cv, None)
     else:
-        r = L.orc.orc_dlevmar_bc_dif(f, L.ptr(p), L.ptr(xx), 3, n, L.ptr(l), L.ptr(u), None, itmax, L.ptr(o), L.ptr(info), None, None, None)
-    return r, p, info
+        r = L.orc.orc_dlevmar_bc_dif(f, L.ptr(p), L.ptr(xx), 3, n, L.ptr(l), L.ptr(u), L.ptr(d), itmax, L.ptr(o), L.ptr(info), None, cv, None)
+    return r, p, info, covar.reshape(3, 3)
 
 
 def _rel(a, b, floor):
@@ -185,19 +211,41 @@ def undefined(info_ref):
     return ("info2", "info4") if info_ref[8] == 0 else ()
 
 
+def covar_difference(c, c_ref):
+    """max over i, j of |C_ij - C_ref_ij| / sqrt(C_ref_ii * C_ref_jj): the difference on the scale of the reference's standard
+    deviations, which removes the parameters' units (inf where either holds a non-finite value or the diagonal is not positive)"""
+    c, c_ref = np.asarray(c, dtype=np.float64).reshape(3, 3), np.asarray(c_ref, dtype=np.float64).reshape(3, 3)
+    d = np.diag(c_ref)
+    if not (np.all(np.isfinite(c)) and np.all(np.isfinite(c_ref)) and np.all(d > 0.0)):
+        return np.inf
+    s = np.sqrt(d)
+    return float(np.max(np.abs(c - c_ref) / np.outer(s, s)))
+
+
+def _proper(c):
+    return bool(np.all(np.isfinite(c)) and np.all(np.diag(c) > 0.0))
+
+
+def _seed(case):
+    """the seed of a case's disturbed runs: that of the four-field Case for a case without dscl"""
+    name = f"Case(problem={case.problem!r}, method={case.method!r}, itmax={case.itmax!r}, opts={case.opts!r})"
+    return zlib.crc32((name if case.dscl is None else repr(case)).encode())
+
+
 @functools.lru_cache(maxsize=None)
 def yardstick(case) -> Yard:
     angles, x, p0, _, _ = problem(case.problem)
     lb, ub = box(case)
+    dscl = scaling(case)
     model = case.problem[1]
-    base = L.brdf_fit("orc", case.method, model, angles, x, p0, case.itmax, case.opts, lb, ub)
-    seed = zlib.crc32(repr(case).encode())
+    base = L.brdf_fit_covar("orc", case.method, model, angles, x, p0, case.itmax, case.opts, lb, ub, dscl)
+    seed = _seed(case)
     runs = []
     for k in range(4):
         perm = np.random.default_rng([seed, k]).permutation(x.size)
-        runs.append(L.brdf_fit("orc", case.method, model, angles[:, perm], x[perm], p0, case.itmax, case.opts, lb, ub))
+        runs.append(L.brdf_fit_covar("orc", case.method, model, angles[:, perm], x[perm], p0, case.itmax, case.opts, lb, ub, dscl))
     for k in range(4):
-        runs.append(_noisy_fit(case.method, model, angles, x, p0, case.itmax, case.opts, lb, ub, np.random.default_rng([seed, 4 + k])))
+        runs.append(_noisy_fit(case.method, model, angles, x, p0, case.itmax, case.opts, lb, ub, np.random.default_rng([seed, 4 + k]), dscl))
     stable = all(r[0] == base[0] and np.array_equal(r[2][5:], base[2][5:]) for r in runs)
     spread = {f: 0.0 for f in FIELDS}
     if case.itmax > 0:  # (itmax = 0: info[2], info[4] are undefined, p == p0 -- nothing to measure)
@@ -208,36 +256,108 @@ def yardstick(case) -> Yard:
         spread[f] = 0.0
     tol = {f: max(MARGIN * s, FLOOR) for f, s in spread.items()}
     comparable = (stable and all(tol[f] <= CAP_P for f in ("p", "info0", "info1")) and all(tol[f] <= CAP_INFO for f in ("info2", "info3", "info4")))
-    return Yard(base[0], base[1], base[2], stable, spread, tol, comparable)
+    settled = all(r[0] >= 0 and r[2][6] in (1.0, 2.0) for r in [base] + runs)
+    # the covariance: nothing defined at itmax = 0, before the first Jacobian, and where orc_covar found J'J singular (the NaN fill
+    # survives); compared where the case is stable (a converged case: settled), all nine are finite with a positive diagonal and
+    # 8 x the spread is within the cap
+    if case.itmax <= 0 or base[2][8] == 0 or np.all(np.isnan(base[3])):
+        rule = "zeros"
+    else:
+        rule = "left out"
+        if (stable or (converged(case) and settled)) and all(_proper(r[3]) for r in [base] + runs):
+            spread["covar"] = max(covar_difference(r[3], base[3]) for r in runs)
+            tol["covar"] = max(MARGIN * spread["covar"], FLOOR)
+            if tol["covar"] <= CAP_INFO:
+                rule = "compare"
+    return Yard(base[0], base[1], base[2], stable, spread, tol, comparable, base[3], rule, settled)
+
+
+def converged(case):
+    """a case of converged_cases: the fit runs to its own end under synth.ITMAX and synth.OPTS"""
+    return case.itmax == synth.ITMAX and case.opts == synth.OPTS
 
 
 # ---- the comparison ---------------------------------------------------------------------------------------------------
-def compare(case, got):
-    """one result (ret, p[3], info[10]) against the oracle's.  -> (compared, ratios, problem): compared is False for a case the
-    yardstick does not admit; ratios: per field, difference / tolerance; problem: None, or what is wrong, in words."""
-    ret, p, info = int(got[0]), np.asarray(got[1], dtype=np.float64), np.asarray(got[2], dtype=np.float64)
-    if case.itmax <= 0:
-        return (True, {}) + (itmax0_problem(case, (ret, p, info)),)
+def covar_problem(case, covar):
+    """a returned covariance against the oracle's.  -> (rule, ratio, problem): rule is the yardstick's covar_rule; ratio: difference /
+    tolerance where it is compared (None otherwise); problem: None, or what is wrong, in words"""
     y = yardstick(case)
-    if not y.comparable:
-        return False, {}, None
-    ratios = {f: d / y.tol[f] for f, d in differences(p, info, y.p, y.info).items() if f not in undefined(y.info)}
-    wrong = []
-    if ret != y.ret:
-        wrong.append(f"ret {ret} != {y.ret}")
-    if not np.array_equal(info[5:], y.info[5:]):
-        wrong.append(f"info[5..9] {info[5:].tolist()} != {y.info[5:].tolist()}")
-    wrong += [f"{f}: {r:.3g} x its tolerance {y.tol[f]:.3g}" for f, r in ratios.items() if not r <= 1.0]
+    c = np.asarray(covar, dtype=np.float64).reshape(3, 3)
+    if y.covar_rule == "zeros":
+        if not (np.array_equal(c, np.zeros((3, 3))) and not np.any(np.signbit(c))):
+            return "zeros", None, f"covar {c.tolist()} where the reference writes none: nine zeros expected"
+        return "zeros", None, None
+    if y.covar_rule != "compare":
+        return y.covar_rule, None, None
+    r = covar_difference(c, y.covar) / y.tol["covar"]
+    return "compare", r, None if r <= 1.0 else f"covar: {r:.3g} x its tolerance {y.tol['covar']:.3g} (got {c.tolist()}, oracle {y.covar.tolist()})"
+
+
+def compare(case, got):
+    """one result (ret, p[3], info[10]) or (ret, p[3], info[10], covar[3,3]) against the oracle's.  -> (compared, ratios, problem):
+    compared is False for a case the yardstick does not admit; ratios: per field, difference / tolerance; problem: None, or what is
+    wrong, in words.  The covariance is judged by its own rule (covar_problem), whether or not the other fields are admitted; a
+    "zeros" case is judged where the other fields are."""
+    ret, p, info = int(got[0]), np.asarray(got[1], dtype=np.float64), np.asarray(got[2], dtype=np.float64)
+    covar = got[3] if len(got) > 3 else None
+    if case.itmax <= 0:
+        wrong = itmax0_problem(case, (ret, p, info))
+        if wrong is None and covar is not None and covar_problem(case, covar)[2]:
+            wrong = f"{describe(case)}: {covar_problem(case, covar)[2]}"
+        return True, {}, wrong
+    y = yardstick(case)
+    if converged(case):
+        return _compare_converged(case, y, ret, p, info, covar)
+    ratios, wrong = {}, []
+    if y.comparable:
+        ratios = {f: d / y.tol[f] for f, d in differences(p, info, y.p, y.info).items() if f not in undefined(y.info)}
+        if ret != y.ret:
+            wrong.append(f"ret {ret} != {y.ret}")
+        if not np.array_equal(info[5:], y.info[5:]):
+            wrong.append(f"info[5..9] {info[5:].tolist()} != {y.info[5:].tolist()}")
+        wrong += [f"{f}: {r:.3g} x its tolerance {y.tol[f]:.3g}" for f, r in ratios.items() if not r <= 1.0]
+    if covar is not None and (y.comparable or y.covar_rule == "compare"):
+        _, r, w = covar_problem(case, covar)
+        if r is not None:
+            ratios["covar"] = r
+        if w:
+            wrong.append(w)
     if wrong:
-        return True, ratios, f"{describe(case)}: " + "; ".join(wrong) + f" (got p {p.tolist()} info {info.tolist()}, oracle p {y.p.tolist()} info {y.info.tolist()})"
-    return True, ratios, None
+        return y.comparable, ratios, f"{describe(case)}: " + "; ".join(wrong) + f" (got p {p.tolist()} info {info.tolist()}, oracle p {y.p.tolist()} info {y.info.tolist()})"
+    return y.comparable, ratios, None
+
+
+def converged_comparable(y):
+    """p of a fit that ran to its own end is as sharp as its stop rule, not as a single pass: the 8 x the spread of the oracle's own p
+    reaches 2.4e-8 (Blinn-Phong dlevmar_dif, n = 1000), so the cap on p is CAP_INFO here; info[1] keeps CAP_P"""
+    return y.settled and y.tol["p"] <= CAP_INFO and y.tol["info1"] <= CAP_P
+
+
+def _compare_converged(case, y, ret, p, info, covar):
+    """a fit that runs to its own end: the counts differ from run to run, so only ret >= 0, p, info[1] and the covariance are judged"""
+    ok = converged_comparable(y)
+    ratios, wrong = {}, []
+    if ok:
+        d = differences(p, info, y.p, y.info)
+        ratios = {f: d[f] / y.tol[f] for f in ("p", "info1")}
+        if ret < 0:
+            wrong.append(f"ret {ret}")
+        wrong += [f"{f}: {r:.3g} x its tolerance {y.tol[f]:.3g}" for f, r in ratios.items() if not r <= 1.0]
+    if covar is not None and y.covar_rule == "compare":
+        _, r, w = covar_problem(case, covar)
+        ratios["covar"] = r
+        if w:
+            wrong.append(w)
+    if wrong:
+        return ok, ratios, f"{describe(case)}: " + "; ".join(wrong) + f" (got p {p.tolist()} info {info.tolist()}, oracle p {y.p.tolist()} info {y.info.tolist()})"
+    return ok, ratios, None
 
 
 def itmax0_problem(case, got):
     """itmax = 0: the reference returns info[2] and info[4] from memory it never wrote (and info[3] from its initial value); what is
     defined is ret = 0, p == p0 bit for bit (for the box methods: p0 projected on the box), info[0] == info[1] == the oracle's,
     info[5] = 0, info[6] = 3, info[7] = 1, info[8] = info[9] = 0"""
-    ret, p, info = got
+    ret, p, info = got[:3]
     y = yardstick(case)
     wrong = []
     if ret != 0 or y.ret != 0:
@@ -253,18 +373,36 @@ def itmax0_problem(case, got):
 
 def describe(case):
     name = next((k for k, v in {**OPTIONS, **STOPS}.items() if v == case.opts), "default" if case.opts == synth.OPTS else str(case.opts))
-    return f"{case.problem} {METHOD[case.method]} itmax={case.itmax} opts:{name}"
+    return f"{case.problem} {METHOD[case.method]} itmax={case.itmax} opts:{name}" + ("" if case.dscl is None else f" dscl:{case.dscl}")
+
+
+def admitted(case):
+    """whether the yardstick admits the case's ret, p and info to the comparison"""
+    y = yardstick(case)
+    return case.itmax <= 0 or (converged_comparable(y) if converged(case) else y.comparable)
+
+
+def covar_judged(case):
+    """whether a returned covariance of the case is judged: compared with the oracle's, or asserted to be nine zeros"""
+    y = yardstick(case)
+    if y.covar_rule == "zeros":
+        return case.itmax <= 0 or y.comparable
+    return y.covar_rule == "compare"
 
 
 class Tally:
-    """what a test prints and asserts about its cases: compared / uncompared per cell, the worst ratio per field"""
+    """what a test prints and asserts about its cases: compared / uncompared per cell, the worst ratio per field; for results that
+    carry a covariance, the same count for the covariance alone"""
 
     def __init__(self, name):
-        self.name, self.cells, self.worst, self.bad = name, collections.defaultdict(lambda: [0, 0]), {f: 0.0 for f in FIELDS}, []
+        self.name, self.cells, self.worst, self.bad = name, collections.defaultdict(lambda: [0, 0]), {f: 0.0 for f in FIELDS + ("covar",)}, []
+        self.covar_cells = collections.defaultdict(lambda: [0, 0])
 
     def add(self, cell, case, got):
         compared, ratios, wrong = compare(case, got)
         self.cells[cell][0 if compared else 1] += 1
+        if len(got) > 3 and got[3] is not None:
+            self.covar_cells[cell][0 if covar_judged(case) else 1] += 1
         for f, r in ratios.items():
             self.worst[f] = max(self.worst[f], r)
         if wrong is not None:
@@ -273,16 +411,20 @@ class Tally:
 
     def summary(self):
         comp, unc = sum(c[0] for c in self.cells.values()), sum(c[1] for c in self.cells.values())
-        return (f"{self.name}: {comp} compared, {unc} uncompared, {len(self.bad)} wrong; worst difference / tolerance: "
-                + ", ".join(f"{f} {r:.2g}" for f, r in self.worst.items()))
+        cov = ""
+        if self.covar_cells:
+            cov = f"covar: {sum(c[0] for c in self.covar_cells.values())} judged, {sum(c[1] for c in self.covar_cells.values())} left out; "
+        return (f"{self.name}: {comp} compared, {unc} uncompared, {len(self.bad)} wrong; {cov}worst difference / tolerance: "
+                + ", ".join(f"{f} {r:.2g}" for f, r in self.worst.items() if f != "covar" or self.covar_cells))
 
     def check(self):
         print(self.summary())
         assert not self.bad, "\n".join(self.bad[:20])
-        comp, unc = sum(c[0] for c in self.cells.values()), sum(c[1] for c in self.cells.values())
-        assert unc <= MAX_UNCOMPARED * (comp + unc), (self.name, comp, unc)
-        empty = [k for k, c in self.cells.items() if c[0] == 0]
-        assert not empty, (self.name, "cells with nothing compared", empty)
+        for what, cells in (("", self.cells), ("covar", self.covar_cells)):
+            comp, unc = sum(c[0] for c in cells.values()), sum(c[1] for c in cells.values())
+            assert unc <= MAX_UNCOMPARED * (comp + unc), (self.name, what, comp, unc)
+            empty = [k for k, c in cells.items() if c[0] == 0]
+            assert not empty, (self.name, what, "cells with nothing compared", empty)
 
 
 # ---- case tables ------------------------------------------------------------------------------------------------------
@@ -384,6 +526,43 @@ def switch_cases(n=5000):
         for method in range(4):
             out += [(METHOD[method], c) for c in first_cases(prob, method) + [Case(prob, method, 0, synth.OPTS)] + stop_cases(prob, method)]
     return out + box_first_cases(n)
+
+
+# the covariance under diagonal scaling: the box methods, itmax 1, 2, 3.  3.0 is no power of two, so scales folded into the sums show
+DSCL = (3.0, 1.0, 0.5)
+COVAR_N = (1000, 5000)
+
+
+@functools.lru_cache(maxsize=None)
+def dscl_cases():
+    return [(METHOD[method], Case(("single", model, n), method, k, synth.OPTS, DSCL)) for model in (0, 1, 2) for n in COVAR_N for method in (1, 2)
+            for k in FIRST_ITMAX]
+
+
+CONVERGED_LARGE_MODEL = {0: 0, 1: 0, 2: 1, 3: 2}  # n = 262145: per method, the model whose nine oracle runs take the least time
+
+
+@functools.lru_cache(maxsize=None)
+def converged_cases(sizes=COVAR_N):
+    """fits that run to their own end (n = 64 stays out: Ward dlevmar_dif ends at itmax there); at n = 262145 one model per method"""
+    return [(METHOD[method], Case(("single", model, n), method, synth.ITMAX, synth.OPTS)) for n in sizes for method in range(4)
+            for model in ((0, 1, 2) if n < 100000 else (CONVERGED_LARGE_MODEL[method],))]
+
+
+def singular_cases():
+    """a J'J that is singular exactly: Phong / Blinn-Phong started with ks = 0 on lb = 0 -- the column of the exponent is ks * (...)
+    = 0 at p and at p + delta, so the Crout LU sees a zero row, orc_covar reports "singular matrix" and leaves covar as it came"""
+    return [(METHOD[method], Case(("zero_ks", model, n), method, 1, synth.OPTS)) for model in (0, 1) for n in (1000, 5000) for method in (1, 2)]
+
+
+@functools.lru_cache(maxsize=None)
+def zero_covar_cases():
+    """[(cell, case)] where the reference writes no covariance: itmax = 0; a stop at the start point before the first Jacobian (the
+    first channel of the channel problems under CHANNEL_OPTS); the singular cases, and the box-active first passes that are singular
+    of themselves"""
+    rows = [(METHOD[method], Case(("channel", model, CHANNEL_N, 0), method, synth.ITMAX, CHANNEL_OPTS)) for model in CHANNEL_TRUTHS for method in range(4)]
+    rows += singular_cases() + [(cell, c) for cell, c in switch_cases() if yardstick(c).covar_rule == "zeros"]
+    return [(cell, c) for cell, c in rows if admitted(c)]
 
 
 # channels: one set of planes (synth.make_single's), three measurement vectors, one opts.  Under CHANNEL_OPTS the first is over at

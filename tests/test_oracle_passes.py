@@ -18,23 +18,37 @@ def _fit(which, case):
     return L.brdf_fit(which, case.method, case.problem[1], angles, x, p0, case.itmax, case.opts, lb, ub)
 
 
+def _fit_covar(which, case):
+    angles, x, p0, _, _ = P.problem(case.problem)
+    lb, ub = P.box(case)
+    return L.brdf_fit_covar(which, case.method, case.problem[1], angles, x, p0, case.itmax, case.opts, lb, ub, P.scaling(case))
+
+
 def _conditions(name, rows):
-    """the 10 % / no-empty-cell conditions of `rows` with the reference alone; -> (compared, uncompared, largest tolerance per field)"""
-    cells = collections.defaultdict(lambda: [0, 0])
-    worst = {f: 0.0 for f in P.FIELDS}
+    """the 10 % / no-empty-cell conditions of `rows` with the reference alone, for ret / p / info and for the covariance;
+    -> (compared, uncompared, largest tolerance per field)"""
+    cells, covar_cells = collections.defaultdict(lambda: [0, 0]), collections.defaultdict(lambda: [0, 0])
+    worst = {f: 0.0 for f in P.FIELDS + ("covar",)}
     for cell, case in rows:
         y = P.yardstick(case)
-        ok = case.itmax <= 0 or y.comparable
+        ok = P.admitted(case)
         cells[cell][0 if ok else 1] += 1
-        if ok and case.itmax > 0:
-            for f in P.FIELDS:
+        covar_cells[cell][0 if P.covar_judged(case) else 1] += 1
+        if ok and case.itmax > 0:  # (a converged case: only p and info[1] are judged, p against CAP_INFO)
+            for f in ("p", "info1") if P.converged(case) else P.FIELDS:
                 worst[f] = max(worst[f], y.tol[f])
+        if y.covar_rule == "compare":
+            worst["covar"] = max(worst["covar"], y.tol["covar"])
     comp, unc = sum(c[0] for c in cells.values()), sum(c[1] for c in cells.values())
-    print(f"{name}: {comp} compared, {unc} uncompared ({100.0 * unc / (comp + unc):.1f} %); largest tolerance: "
-          + ", ".join(f"{f} {v:.2g}" for f, v in worst.items()))
+    cj, cl = sum(c[0] for c in covar_cells.values()), sum(c[1] for c in covar_cells.values())
+    print(f"{name}: {comp} compared, {unc} uncompared ({100.0 * unc / (comp + unc):.1f} %); covar: {cj} judged, {cl} left out "
+          f"({100.0 * cl / (cj + cl):.1f} %); largest tolerance: " + ", ".join(f"{f} {v:.2g}" for f, v in worst.items()))
     assert unc <= P.MAX_UNCOMPARED * (comp + unc), (name, comp, unc)
     assert all(c[0] > 0 for c in cells.values()), (name, dict(cells))
-    assert all(worst[f] <= P.CAP_P for f in ("p", "info0", "info1")) and all(worst[f] <= P.CAP_INFO for f in ("info2", "info3", "info4"))
+    assert cl <= P.MAX_UNCOMPARED * (cj + cl), (name, "covar", cj, cl)
+    assert all(c[0] > 0 for c in covar_cells.values()), (name, "covar", dict(covar_cells))
+    cap_p = P.CAP_INFO if all(P.converged(c) for _, c in rows) else P.CAP_P
+    assert worst["p"] <= cap_p and all(worst[f] <= P.CAP_P for f in ("info0", "info1")) and all(worst[f] <= P.CAP_INFO for f in ("info2", "info3", "info4", "covar"))
     return comp, unc, worst
 
 
@@ -63,6 +77,15 @@ def test_gpu_case_lists_meet_their_conditions():
         if regime != "short_last_workgroup":  # (n = 262145: eight cases, judged on the GPU machine)
             _conditions(f"single fits, {regime}", [r for n in sizes for r in P.single_cases(n)])
     _conditions("switches", P.switch_cases())
+    _conditions("diagonal scaling", P.dscl_cases())
+    _conditions("converged fits", P.converged_cases())
+    zeros = [c for _, c in P.zero_covar_cases()]
+    assert all(P.yardstick(c).covar_rule == "zeros" for c in zeros) and sum(c.itmax == 0 for c in zeros) == 12
+    assert sum(c.itmax > 0 and P.yardstick(c).info[8] == 0 for c in zeros) >= 8 and sum(P.yardstick(c).info[8] > 0 for c in zeros) >= 16
+    for _, case in P.singular_cases():  # J'J singular exactly: the oracle says so and its NaN fill survives, with and without noise
+        y = P.yardstick(case)
+        assert y.comparable and y.covar_rule == "zeros" and y.info[8] == 1 and np.all(np.isnan(y.covar)), (P.describe(case), y)
+        assert np.all(np.isnan(_fit_covar("orc", case)[3]))
     _conditions("channels", [(P.METHOD[method], c) for model in P.CHANNEL_TRUTHS for method in range(4)
                              for row in P.channel_cases(model, method) for c in row])
     for model in P.CHANNEL_TRUTHS:
@@ -104,8 +127,9 @@ def test_oracle_equals_the_compiled_reference_at_these_settings():
 
 @pytest.mark.parametrize("which", ["hm", "hm_fast"])
 def test_host_driven_machines_pass_the_gpu_comparison(which):
-    """the product's DifMachine / BcMachine / DerMachine with reference-order sums.  hm: the oracle's expressions, so it must
-    equal the oracle bit for bit wherever the reference defines the result; hm_fast: within the case's tolerance"""
+    """the product's DifMachine / BcMachine / DerMachine with reference-order sums, covariance and dscl included.  hm: the oracle's
+    expressions, so without dscl it must equal the oracle bit for bit wherever the reference defines the result (and return nine
+    zeros where the reference writes no covariance); hm_fast, and hm with dscl: within the case's tolerance"""
     rows = [r for rows in P.tables().values() for r in rows]
     rows += [r for n in (64, 1000, 4096, 5000) for r in P.single_cases(n)]
     for model in P.CHANNEL_TRUTHS:
@@ -113,15 +137,20 @@ def test_host_driven_machines_pass_the_gpu_comparison(which):
             rows += [(P.METHOD[method], c) for row in P.channel_cases(model, method) for c in row]
     for kernel in P.BATCH_KERNELS:
         rows += P.batch_rows(kernel)
+    rows += P.dscl_cases() + P.converged_cases() + P.singular_cases()
     rows = list(dict.fromkeys(rows))
     tally = P.Tally(f"host-driven machines, {which}")
     for cell, case in rows:
-        got = _fit(which, case)
+        got = _fit_covar(which, case)
         tally.add(cell, case, got)
-        if which == "hm" and case.itmax > 0:
+        if which == "hm" and case.itmax > 0 and case.dscl is None:
             y = P.yardstick(case)
             keep = [i for i in range(10) if f"info{i}" not in P.undefined(y.info)]
             assert got[0] == y.ret and np.array_equal(got[1], y.p) and np.array_equal(got[2][keep], y.info[keep], equal_nan=True), (P.describe(case), got, y)
+            if y.covar_rule == "zeros":  # (nothing defined in the reference: nine zeros here)
+                assert got[3].tobytes() == np.zeros((3, 3)).tobytes(), (P.describe(case), got[3])
+            else:  # (a J'J that is singular to round-off alone gives inf / NaN on both sides)
+                assert np.array_equal(got[3], y.covar, equal_nan=True), (P.describe(case), got[3], y.covar)
     tally.check()
 
 
