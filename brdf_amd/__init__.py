@@ -10,4 +10,5 @@ from .fit import (METHOD_BC_DER, METHOD_BC_DIF, METHOD_DER, METHOD_DIF, MODEL_BL
                   cosines, compact_samples, fit_capture, fit_capture_masked, fit_capture_single, fit_channels, fit_single, last_channels_stats, host_dlevmar, last_fit_stats, last_multi_stats, led_table, model_eval, chkjac, model_jacobian, set_launch_timing,
                   fit_batch_packed, fit_stats_batch_packed, last_packed_stats, pack_samples,
                   CaptureFaces, fit_capture_faces, group_capture_samples,
-                  fit_batch_weighted, fit_stats_batch_weighted, CaptureMeans, LightMeans, fit_capture_means, capture_light_means)
+                  fit_batch_weighted, fit_stats_batch_weighted, CaptureMeans, LightMeans, fit_capture_means, capture_light_means,
+                  CaptureSingleFaces, SingleSamples, fit_capture_single_faces, group_capture_single_samples)

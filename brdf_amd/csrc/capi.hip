@@ -791,6 +791,28 @@ int brdf_hip_fit_capture_single_dev(int model, const unsigned char *d_images, in
                                 rv_mode, p0, lb, ub, itmax, opts, single_brdf, info, n_faces_used, static_cast<hipStream_t>(stream));
 }
 
+int brdf_hip_fit_capture_single_faces_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                          const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                          const double *view_origin, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
+                                          const double *opts, int v_min, int v_max, double cos_min, double *single_brdf, double *info, int *ret,
+                                          double *covar, double *stats, int *rank, long long *count, double *d_face_sumsq, int *d_face_count,
+                                          int *d_face_pixels, long long *n_pixels, long long *n_faces, void *stream) {
+  CaptureSingleFacesArgs a = {};
+  a.cap = {model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin, rv_mode, p0, lb, ub,
+           itmax, opts, v_min, v_max, cos_min, 0, nullptr, nullptr, nullptr, nullptr,
+           nullptr, nullptr, nullptr, d_face_pixels, nullptr, n_pixels, n_faces, static_cast<hipStream_t>(stream)};
+  a.single_brdf = single_brdf;
+  a.info = info;
+  a.ret = ret;
+  a.covar = covar;
+  a.stats = stats;
+  a.rank = rank;
+  a.count = count;
+  a.d_face_sumsq = d_face_sumsq;
+  a.d_face_count = d_face_count;
+  return capture_single_faces_run(a);
+}
+
 int brdf_hip_device_count(void) {
   int c = 0;
   if (hipGetDeviceCount(&c) != hipSuccess) return 0;

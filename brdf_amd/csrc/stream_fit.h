@@ -154,6 +154,22 @@ struct CaptureFacesArgs {
 };
 int capture_faces_run(const CaptureFacesArgs &a);  // refuses bad arguments before any HIP call
 
+// brdf_hip_fit_capture_single_faces_dev (capture_single_faces.hip): ONE fit per channel over the valid samples of every pixel of every
+// carried face, through the single-fit path, and the carried faces' sums of squared residuals against that fit.
+struct CaptureSingleFacesArgs {
+  CaptureFacesArgs cap;  // the capture, the mesh, the fit's settings, the rule, d_face_pixels, n_pixels, n_faces, stream; its
+                         // workspace_bytes, [nf][3] maps and avg are not read
+  double *single_brdf;   // host [3][3], required
+  double *info;          // host [3][10] or null
+  int *ret;              // host [3] or null
+  double *covar, *stats;  // host [3][9], [3][kStatsSz] or null
+  int *rank;              // host [3] or null
+  long long *count;       // host [3] or null: the samples of channel c's fit
+  double *d_face_sumsq;   // [nf][3] or null
+  int *d_face_count;      // [nf][3] or null
+};
+int capture_single_faces_run(const CaptureSingleFacesArgs &a);  // refuses bad arguments before any HIP call; the channels with ret < 0
+
 // one model evaluation / analytic Jacobian over n samples (stream_fit.hip): d_hx [n], d_jac [n][3]
 int model_eval_run(int model, const double *d_angles, int n, const double *p, double *d_hx, hipStream_t stream);
 int model_jac_run(int model, const double *d_angles, int n, const double *p, double *d_jac, hipStream_t stream);

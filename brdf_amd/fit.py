@@ -803,6 +803,89 @@ def fit_capture_single(model: int, images, pixel_map, vertices, faces, face_norm
     return out.reshape(3, 3), info.reshape(3, 10), nfu.value
 
 
+class CaptureSingleFaces(NamedTuple):
+    """What fit_capture_single_faces returns: the three channels' fits (NumPy), the face maps (CUDA tensors) and the host scalars."""
+    single_brdf: np.ndarray  # [3,3] float64: {kd, ks, n} per channel (B, G, R)
+    info: np.ndarray         # [3,10] float64: levmar's info[]
+    ret: np.ndarray          # [3] int32: iterations, or -1
+    count: np.ndarray        # [3] int64: K_c, the samples of the channel's fit
+    stats: FitStats | None   # host covar [3,3,3], stats [3,8], rank [3]; None without want_stats
+    face_sumsq: object       # [nf,3] float64: the face's sum of squared residuals against the channel's fit
+    face_count: object       # [nf,3] int32: the face's samples in the channel
+    face_pixels: object      # [nf] int32: the pixels that carry the face (0 where none)
+    n_pixels: int
+    n_faces: int
+
+
+def fit_capture_single_faces(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, v_min: int = 0, v_max: int = 255,
+                             cos_min: float = -2.0, rv_mode: int = 0, p0=(0.5, 1.0, 1.0), lb=(0.0, 0.0, 0.0), ub=(100.0, 100.0, 100.0),
+                             itmax: int = 100, opts=None, want_stats: bool = True, validate: bool = True,
+                             out: CaptureSingleFaces | None = None) -> CaptureSingleFaces:
+    """ONE fit per colour channel for the whole object over the valid samples of EVERY pixel of every carried face
+    (brdf_hip_fit_capture_single_faces_dev), where fit_capture_single takes each face's last pixel and knows no validity rule.
+    Arguments as fit_capture; the validity rule as fit_capture_masked (the defaults switch it off).  Channel c's samples are those of
+    fit_capture_faces' fits (face, c), ascending faces one behind the other -- group_capture_single_samples is this definition as
+    code -- and single_brdf / info / ret have the bytes of fit_single(METHOD_BC_DIF, ...) on them, stats those of fit_stats_batch
+    with S = 1.  A channel of fewer than 3 samples is refused: ret -1, zero info, p0, rank 0.  face_sumsq[f, c] is the face's sum of
+    squared residuals against channel c's fit, face_count[f, c] its samples; faces no pixel carries keep what the maps held: zeros, or
+    the values of `out`, an earlier result (or one built by hand) whose three tensors are written into.  The call waits for the
+    stream."""
+    import torch
+    args, keep, nf = _capture_args(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, rv_mode, p0, lb, ub, itmax, opts,
+                                   validate)
+    _require(args[13] is not None, "p0 is required")
+    dev = keep[0].device
+    if out is None:
+        face_sumsq = torch.zeros((nf, 3), dtype=torch.float64, device=dev)
+        face_count = torch.zeros((nf, 3), dtype=torch.int32, device=dev)
+        face_pixels = torch.zeros((nf,), dtype=torch.int32, device=dev)
+    else:
+        face_sumsq, face_count, face_pixels = out.face_sumsq, out.face_count, out.face_pixels
+    for t, shape, dtype in ((face_sumsq, (nf, 3), torch.float64), (face_count, (nf, 3), torch.int32), (face_pixels, (nf,), torch.int32)):
+        _require(t.is_cuda and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(),
+                 f"out: contiguous CUDA {dtype} {list(shape)} tensors on the capture's device")
+    single, info, ret, count = np.zeros((3, 3)), np.zeros((3, 10)), np.zeros(3, dtype=np.int32), np.zeros(3, dtype=np.int64)
+    st = _zero_stats((3,)) if want_stats else None
+    npx, nfc = C.c_longlong(0), C.c_longlong(0)
+    name = "brdf_hip_fit_capture_single_faces_dev"
+    with torch.cuda.device(dev):  # (not _call: the entry returns the number of refused or failed channels)
+        rc = getattr(lib, name)(*args, int(v_min), int(v_max), float(cos_min), _dptr(single), _dptr(info), _iptr(ret),
+                                None if st is None else _dptr(st.covar), None if st is None else _dptr(st.stats),
+                                None if st is None else _iptr(st.rank), count.ctypes.data_as(C.POINTER(C.c_longlong)), face_sumsq.data_ptr(),
+                                face_count.data_ptr(), face_pixels.data_ptr(), C.byref(npx), C.byref(nfc), _stream_handle(torch))
+    if rc < 0:
+        raise RuntimeError(f"{name} failed: {last_error()}")
+    return CaptureSingleFaces(single, info, ret, count, st, face_sumsq, face_count, face_pixels, npx.value, nfc.value)
+
+
+class SingleSamples(NamedTuple):
+    """What group_capture_single_samples returns (NumPy)."""
+    channels: tuple          # per channel (angles [3,K_c] float64, x [K_c] float64, face_offsets [F+1] int64: where a face's samples start)
+    faces: np.ndarray        # [F] int32: the carried faces, ascending
+    face_pixels: np.ndarray  # [nf] int32
+
+
+def group_capture_single_samples(images, pixel_map, face_angles, model: int, *, v_min: int = 0, v_max: int = 255,
+                                 cos_min: float = -2.0) -> SingleSamples:
+    """The host twin of fit_capture_single_faces' sample sets (NumPy, no device): its definition as code.  Arguments, candidates and
+    validity rule as group_capture_samples; channel c's sample set is the concatenation, over the carried faces in ascending order, of
+    the sample sets group_capture_samples gives for (face, c), laid out as a single fit reads it."""
+    a, x, off, fit_face, fit_channel, face_pixels = group_capture_samples(images, pixel_map, face_angles, model, v_min=v_min, v_max=v_max,
+                                                                          cos_min=cos_min)
+    carried = np.ascontiguousarray(fit_face[0::3], dtype=np.int32)  # (fits: ascending face, then channel)
+    channels = []
+    for c in range(3):
+        planes, xs, face_offsets = [np.zeros((3, 0))], [np.zeros(0)], [0]
+        for s in range(c, len(fit_face), 3):
+            k = int(off[s + 1] - off[s])
+            planes.append(a[3 * off[s]:3 * off[s + 1]].reshape(3, k))
+            xs.append(x[off[s]:off[s + 1]])
+            face_offsets.append(face_offsets[-1] + k)
+        channels.append((np.ascontiguousarray(np.concatenate(planes, axis=1)), np.ascontiguousarray(np.concatenate(xs)),
+                         np.array(face_offsets, dtype=np.int64)))
+    return SingleSamples(tuple(channels), carried, face_pixels)
+
+
 def host_dlevmar(method: int, model: int, angles: np.ndarray, x: np.ndarray, p0, *, lb=None, ub=None, dscl=None,
                  itmax=100, opts=None, want_covar=False) -> FitResult:
     """The drop-in call exactly as brdfdata.cpp:1058/1119 makes it: HOST arrays, a BRDFFunc-style callback

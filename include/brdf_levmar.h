@@ -442,7 +442,7 @@ int brdf_hip_fit_capture_stats_dev(int model, const unsigned char *d_images, int
  * brdf_hip_fit_capture_stats_dev wherever the cosines are numbers.  A NaN cosine is never a sample, also with the rule switched off;
  * on such a face (a degenerate triangle with a NaN normal) the rule-off call refuses the fit -- count 0, p0 in d_brdf_surfaces,
  * sumsq = R2 = 0 -- where the unmasked capture stops it with reason 7: p0 as well, but a NaN sumsq and R2.  Returns LM_ERROR for v_min > v_max as for the other bad arguments, before any HIP call.
- * Not covered: brdf_hip_fit_capture_single_dev (masking there changes one big fit's n) and the multi-GPU batch. */
+ * The same rule for the single-BRDF fit is brdf_hip_fit_capture_single_faces_dev below.  Not covered: the multi-GPU batch. */
 int brdf_hip_fit_capture_masked_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
                                     const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf,
                                     const double *leds, const double *view_origin, int rv_mode, const double *p0,
@@ -489,7 +489,7 @@ int brdf_hip_fit_capture_masked_dev(int model, const unsigned char *d_images, in
  *   Empty capture  no carried face: returns 0 with n_pixels = n_faces = 0 and a zero avg; nothing is written but d_face_pixels.
  * Synchronises `stream` before returning.  Returns 0, or LM_ERROR with a message that names the entry in brdf_hip_last_error().
  * The count-weighted fit of per-light means -- the same minimiser from at most L samples per fit -- is brdf_hip_fit_capture_means_dev
- * below (L <= 16).  Not covered: a grouped brdf_hip_fit_capture_single_dev. */
+ * below (L <= 16); the single-BRDF fit over the same grouped samples is brdf_hip_fit_capture_single_faces_dev. */
 int brdf_hip_fit_capture_faces_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
                                    const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
                                    const double *view_origin, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
@@ -548,6 +548,53 @@ int brdf_hip_fit_capture_single_dev(int model, const unsigned char *d_images, in
                                     const double *leds, const double *view_origin, int rv_mode, const double *p0,
                                     const double *lb, const double *ub, int itmax, const double *opts, double *single_brdf,
                                     double *info, long long *n_faces_used, void *stream);
+
+/* The single-BRDF fit over EVERY valid sample: one {kd, ks, n} per colour channel for the whole object, fitted with dlevmar_bc_dif to
+ * the samples of all pixels of all carried faces under the validity rule, where brdf_hip_fit_capture_single_dev takes each face's last
+ * pixel and every light; with covariance and R2, and with the carried faces' residuals against the one fit: where on the object the
+ * one-material assumption fails.  No fit or statistics kernel of its own.  Capture, mesh, leds, view_origin, rv_mode, p0 / lb / ub /
+ * itmax / opts as brdf_hip_fit_capture_dev.
+ *   Validity rule  that of brdf_hip_fit_capture_masked_dev / brdf_hip_fit_capture_faces_dev, word for word: 0, 255, cos_min < -1
+ *                  switches it off; a NaN cosine is never a sample.
+ *   Samples        of channel c (B, G, R): the carried faces in ascending order, within a face its pixels in the reference's walk (x
+ *                  outer, y inner), within a pixel the lights 0 ... L-1, those the rule leaves -- the sample sets of
+ *                  brdf_hip_fit_capture_faces_dev's fits (f, c), one behind the other.  The planes are the face's cosines, the
+ *                  measurement is value / 255.0; K_c samples, laid out as a single fit reads them: planes [3][K_c], x [K_c].
+ *   Fit            K_c >= 3: single_brdf[c], info[c], ret[c] are the BYTES brdf_hip_fit_dev(BRDF_METHOD_BC_DIF, model, ..., n = K_c,
+ *                  p0, lb, ub, dscl = NULL, itmax, opts, ...) returns on that sample set (ret[c]: its return value), under the same
+ *                  environment switches: every single-fit regime is the existing one, the resident launch and the launch chain.
+ *   Statistics     covar[c], stats[c], rank[c]: the bytes of brdf_hip_fit_stats_batch_ragged_dev (BRDF_METHOD_BC_DIF) with S = 1,
+ *                  stride max(K_c, 3) and counts = {K_c} at single_brdf[c]; for K_c >= 3 those of brdf_hip_fit_stats_batch_dev at
+ *                  S = 1, n = K_c: K_c - 3 degrees of freedom.
+ *   Too few        K_c < 3 is levmar's n < m refusal: ret[c] = LM_ERROR, info[c] all zeros, single_brdf[c] = p0, rank[c] = 0.  The
+ *                  other channels are not affected.
+ *   Face maps      d_face_count[nf][3] (DEVICE, may be NULL): the samples of (face f, channel c); d_face_sumsq[nf][3] (DEVICE, may be
+ *                  NULL): the sum over them of (x_i - f(single_brdf[c]; sample i))^2, the model on the exact path (the reference's
+ *                  own pow expression), as the statistics pass evaluates it.  A carried face whose samples the rule removed gets 0.0
+ *                  and 0; faces no pixel carries are left untouched in both.  d_face_pixels[nf] (DEVICE, may be NULL) is written
+ *                  for EVERY face.  A face's samples are cut into chunks of 1024 counted from its own first sample; a chunk is
+ *                  summed by one fixed tree, the chunks' sums are added in ascending order: no float atomics, two calls give the same
+ *                  bytes, and a face's value depends on its own samples, their order and single_brdf[c] only.  In exact arithmetic
+ *                  the sum over f of d_face_sumsq[f][c] is stats[c][0] and info[c][1].
+ *   Host outputs   single_brdf[3][3] (required); info[3][10], ret[3], covar[3][9], stats[3][BRDF_STATS_SZ], rank[3], count[3] (= K_c):
+ *                  each may be NULL.  n_pixels: the pixels that carry a face; n_faces: the carried faces.
+ *   Memory         32 bytes per valid sample (planes and measurement; no second copy of the planes), 24 bytes per carried pixel and
+ *                  the sort's scratch for the grouping, 8 bytes per residual chunk.
+ *   Refused before any HIP call, under the entry's name: a NULL required pointer (images, map, mesh, leds, view origin, p0,
+ *                  single_brdf), L outside [1, 64], H, W or nf <= 0, 3 nf > INT_MAX, an unknown model, v_min > v_max, a NaN cos_min,
+ *                  lb > ub.  Refused once the counts are known: K_c > INT_MAX.
+ *   Empty capture  no carried face: every channel is refused, the call returns 3 with n_pixels = n_faces = 0, zero statistics, and
+ *                  nothing is written on the device but d_face_pixels.
+ * Synchronises `stream` before returning.  Returns the number of channels whose ret is LM_ERROR (0 ... 3), as brdf_hip_fit_batch
+ * counts failed fits; LM_ERROR itself for bad arguments or a HIP failure, with a message that names the entry in
+ * brdf_hip_last_error().  Not covered: the count-weighted fit of per-(face, light) means for the single BRDF (the single-fit regimes
+ * take no weights), dscl, a multi-GPU variant. */
+int brdf_hip_fit_capture_single_faces_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                          const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                          const double *view_origin, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
+                                          const double *opts, int v_min, int v_max, double cos_min, double *single_brdf, double *info, int *ret,
+                                          double *covar, double *stats, int *rank, long long *count, double *d_face_sumsq, int *d_face_count,
+                                          int *d_face_pixels, long long *n_pixels, long long *n_faces, void *stream);
 
 /* ---- diagnostics ----------------------------------------------------------------------------------- */
 int brdf_hip_device_count(void);
