@@ -8,7 +8,7 @@ from . import synth  # noqa: F401
 from ._lib import LIB_PATH, lib, last_error  # noqa: F401
 from .fit import (METHOD_BC_DER, METHOD_BC_DIF, METHOD_DER, METHOD_DIF, MODEL_BLINN_PHONG, MODEL_PHONG, MODEL_WARD, FitResult, FitStats, fit_batch, fit_batch_multi, fit_stats_batch,  # noqa: F401
                   cosines, compact_samples, fit_capture, fit_capture_masked, fit_capture_single, fit_channels, fit_single, last_channels_stats, host_dlevmar, last_fit_stats, last_multi_stats, led_table, model_eval, chkjac, model_jacobian, set_launch_timing,
-                  fit_batch_packed, fit_stats_batch_packed, last_packed_stats, pack_samples,
+                  fit_batch_packed, fit_stats_batch_packed, last_packed_stats, pack_samples, last_batch_launch,
                   CaptureFaces, fit_capture_faces, group_capture_samples,
                   fit_batch_weighted, fit_stats_batch_weighted, CaptureMeans, LightMeans, fit_capture_means, capture_light_means,
                   CaptureSingleFaces, SingleSamples, fit_capture_single_faces, group_capture_single_samples)

@@ -80,6 +80,7 @@ ABI = {
                                                       C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "brdf_hip_fit_stats_batch_packed": (C.c_int, [C.c_int, C.c_int, D, D, C.POINTER(C.c_longlong), C.c_int, D, D, D, D, I, C.c_longlong]),
     "brdf_hip_last_packed_stats": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), I, I]),
+    "brdf_hip_last_batch_launch": (C.c_int, [I, I, C.POINTER(C.c_longlong), I, I]),
     "brdf_hip_model_eval_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, D, C.c_void_p, C.c_void_p]),
     "brdf_hip_synth_dev": (C.c_int, [C.c_int, C.c_ulonglong, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),

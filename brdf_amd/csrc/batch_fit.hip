@@ -674,6 +674,7 @@ int rows_enqueue(int model, int machine, const BatchCtx &c, const int *counts, b
   long long waves = (long long)cus * 16;  // 4 waves per SIMD
   const long long need = ((long long)c.S + kRowsPerWave - 1) / kRowsPerWave;
   if (waves > need) waves = need;
+  note_batch_launch(kLaunchRows, machine == kDifMachine ? 4 : 2, waves);
   return launch_fast_then_exact(fast, model != MODEL_WARD, c.flags, (size_t)c.S, queue, stream, [&](bool fast_kernel, int *q) {
     if (counts)
       hipLaunchKernelGGL(rows_kernel<true>(model, machine, fast_kernel), dim3((unsigned)waves), dim3(kWave), 0, stream, ragged_ctx(c, counts), q);
@@ -725,6 +726,8 @@ int batch_fit_launches(const BatchFitArgs &a, MethodSpec ms, const Geometry &g, 
     c.chain = batch_dif_chain();
     return resident_batch_enqueue(a.model, method, fast, c, a.d_counts, a.stream);
   }
+  note_batch_launch(g.threads == 512 ? kLaunchBig512 : (g.threads == 256 ? kLaunchWorkgroup : kLaunchWave), (g.threads == 64 && g.spt == 1) ? 4 : 2,
+                    a.S);  // (batch_waves_per_simd)
   // fits with a cosine <= 0 mark themselves: second launch on the exact path (Ward's prepared path has no domain restriction)
   return launch_fast_then_exact(fast, a.model != MODEL_WARD, flags, (size_t)a.S, nullptr, a.stream, [&](bool fast_kernel, int *) {
     if (a.d_counts)

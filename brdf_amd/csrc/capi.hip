@@ -705,6 +705,16 @@ int brdf_hip_last_packed_stats(int cls, long long *fits, int *stride, int *chunk
   return 0;
 }
 
+int brdf_hip_last_batch_launch(int *kernel, int *waves_per_simd, long long *grid, int *quorum, int *maxwait) {
+  const BatchLaunchRecord r = last_batch_launch();
+  if (kernel) *kernel = r.kernel;
+  if (waves_per_simd) *waves_per_simd = r.waves_per_simd;
+  if (grid) *grid = r.grid;
+  if (quorum) *quorum = r.quorum;
+  if (maxwait) *maxwait = r.maxwait;
+  return r.kernel < 0 ? LM_ERROR : 0;
+}
+
 int brdf_hip_model_eval_dev(int model, const double *d_angles, int n, const double *p, double *d_hx, void *stream) {
   return model_eval_run(model, d_angles, n, p, d_hx, static_cast<hipStream_t>(stream));
 }

@@ -187,6 +187,27 @@ bool box_refused(MethodSpec ms, const double *lb, const double *ub, const char *
 // a BigFit's (batch_fit.h) three plane prefixes [0, k) next to each other in `pack`, as a single fit reads them (k < stride: a ragged fit)
 int pack_plane_prefixes(const BigFit &f, DeviceBlock<double> &pack, hipStream_t stream);
 
+// ---- which kernel a batched call launched -------------------------------------------------------------------------------------
+// The calling thread's last batched launch (brdf_hip_last_batch_launch): every enqueue below the batched entries notes the kernel it
+// chose and the geometry and scheduler values it passed.  Host words only: what a test reads to know that a switch was obeyed.
+enum BatchKernelCode {
+  kLaunchLane = 0,       // lane_fit.hip: one lane per fit
+  kLaunchRows = 1,       // four fits per wave
+  kLaunchWave = 2,       // one wave per fit (n <= 256)
+  kLaunchWorkgroup = 3,  // 256 threads per fit (n <= 1024)
+  kLaunchEightWave = 4,  // resident_fit.hip's batched kernel (1024 < n <= 4096)
+  kLaunchBig512 = 5,     // the symmetric 512 x 8 geometry
+  kLaunchWeightedLane = 6,
+};
+struct BatchLaunchRecord {
+  int kernel = -1;         // a BatchKernelCode; -1: this thread has launched none
+  int waves_per_simd = 0;  // the chosen instance's launch bound (the lane kernels: BRDF_HIP_LANE_WAVES); 0: the kernel states none
+  long long grid = 0;      // workgroups of the fast (or only) launch
+  int quorum = 0, maxwait = 0;  // the lane kernels' scheduler values; 0 elsewhere
+};
+void note_batch_launch(int kernel, int waves_per_simd, long long grid, int quorum = 0, int maxwait = 0);
+BatchLaunchRecord last_batch_launch();
+
 // ---- fast, then exact -----------------------------------------------------------------------------------------------------
 // Batched: launch(true, queue) enqueues the prepared-sample kernel, launch(false, queue + 1) its exact twin over the fits that
 // marked themselves kNeedsExact (a cosine <= 0).  fast == false (BRDF_HIP_EXACT_POW=1): every fit is marked and only the exact

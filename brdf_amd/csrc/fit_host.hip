@@ -62,6 +62,16 @@ bool box_refused(MethodSpec ms, const double *lb, const double *ub, const char *
   return false;
 }
 
+static thread_local BatchLaunchRecord g_batch_launch;
+void note_batch_launch(int kernel, int waves_per_simd, long long grid, int quorum, int maxwait) {
+  g_batch_launch.kernel = kernel;
+  g_batch_launch.waves_per_simd = waves_per_simd;
+  g_batch_launch.grid = grid;
+  g_batch_launch.quorum = quorum;
+  g_batch_launch.maxwait = maxwait;
+}
+BatchLaunchRecord last_batch_launch() { return g_batch_launch; }
+
 int pack_plane_prefixes(const BigFit &f, DeviceBlock<double> &pack, hipStream_t stream) {
   HIP_OK(pack.ensure(3 * (size_t)f.stride));
   for (int pl = 0; pl < 3; ++pl)

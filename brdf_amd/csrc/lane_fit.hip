@@ -326,6 +326,7 @@ int lane_fit_enqueue(int model, bool fast, const BatchCtx &c, const int *counts,
   long long waves = (long long)cus * per_cu;
   const long long need = ((long long)c.S + kWave - 1) / kWave;
   if (waves > need) waves = need;
+  note_batch_launch(kLaunchLane, w, waves, cc.lane_quorum, cc.lane_maxwait);
   // (a launch over an empty set costs one queue sweep: every lane's first fetch finds no marked fit)
   return launch_fast_then_exact(fast, model != MODEL_WARD, c.flags, (size_t)c.S, queue, stream, [&](bool fast_kernel, int *q) {
     if (counts)

@@ -157,6 +157,7 @@ int resident_batch_enqueue(int model, int method, bool fast, const BatchCtx &c, 
     return kLmError;
   }
   const ResidentKernels k = kKernels[model][method]();
+  note_batch_launch(kLaunchEightWave, 0, c.S);
   return launch_fast_then_exact(fast, k.batched[kExactPath] != nullptr, c.flags, (size_t)c.S, nullptr, stream, [&](bool fast_kernel, int *) {
     if (counts)  // per-fit sample counts: the RAGGED instances
       hipLaunchKernelGGL(k.ragged[fast_kernel ? kFastPath : kExactPath], dim3(c.S), dim3(kRThreads), 0, stream, ResidentCtx{}, ragged_ctx(c, counts));

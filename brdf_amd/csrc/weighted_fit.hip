@@ -310,6 +310,7 @@ int weighted_launches(const WeightedFitArgs &wa, MethodSpec ms, int *flags, int 
   long long waves = (long long)cus * per_cu;
   const long long need = ((long long)a.S + kWave - 1) / kWave;
   if (waves > need) waves = need;
+  note_batch_launch(kLaunchWeightedLane, w, waves, c.lane_quorum, c.lane_maxwait);
   const bool fast = brdf_fast_path_enabled() || a.model == MODEL_WARD;
   return launch_fast_then_exact(fast, a.model != MODEL_WARD, flags, (size_t)a.S, queue, a.stream, [&](bool fast_kernel, int *q) {
     hipLaunchKernelGGL(weighted_kernel(a.model, fast_kernel, w), dim3((unsigned)waves), dim3(kWave), lds, a.stream, c, q);

@@ -110,22 +110,29 @@ def fit_single(method: int, model: int, angles, x, p0, *, lb=None, ub=None, dscl
                      buf[_OFF_COVAR:_OFF_COVAR + 9].reshape(3, 3).copy() if want_covar else None)
 
 
-def fit_channels(method: int, model: int, angles, x, p0, *, lb=None, ub=None, dscl=None, itmax=100, opts=None, want_covar=False):
+def fit_channels(method: int, model: int, angles, x, p0, *, lb=None, ub=None, dscl=None, itmax=100, opts=None, want_covar=False,
+                 x_stride=None):
     """K fits over ONE set of planes (brdf_hip_fit_channels_dev): the three colour channels of a capture, as the reference's
     callers fit them (brdfdata.cpp:1159-1181).  angles: CUDA float64 [3,n]; x: CUDA float64 [K,n]; p0: [K,3] (or [3]: the same
-    start for every channel).  Returns a list of K FitResult; `last_channels_stats()` tells whether they shared one launch."""
+    start for every channel).  x_stride (optional): x is [K,x_stride] and channel c's n = angles.numel() / 3 measurements are the
+    first n of its row (the ABI's x_stride > n; what lies behind them is never read).
+    Returns a list of K FitResult; `last_channels_stats()` tells whether they shared one launch."""
     import torch
     _require(angles.is_cuda and x.is_cuda and angles.dtype == torch.float64 and x.dtype == torch.float64, "angles, x: CUDA float64 tensors")
     angles, x = angles.contiguous(), x.contiguous()
-    _require(x.dim() == 2 and angles.numel() == 3 * x.shape[1], "angles [3,n], x [K,n]")
-    K, n = int(x.shape[0]), int(x.shape[1])
+    if x_stride is None:
+        _require(x.dim() == 2 and angles.numel() == 3 * x.shape[1], "angles [3,n], x [K,n]")
+        x_stride = int(x.shape[1])
+    _require(x.dim() == 2 and angles.numel() % 3 == 0 and int(x.shape[1]) == int(x_stride) >= angles.numel() // 3 > 0,
+             "angles [3,n], x [K,x_stride] with x_stride >= n")
+    K, n = int(x.shape[0]), angles.numel() // 3
     p = np.ascontiguousarray(np.broadcast_to(np.asarray(p0, dtype=np.float64).reshape(-1, 3), (K, 3))).copy()
     info = np.zeros((K, 10))
     covar = np.zeros((K, 9)) if want_covar else None
     lba, uba, dsa = _f64(lb, 3), _f64(ub, 3), _f64(dscl, 3)
     oa = _f64(opts, 5) if opts is not None else None
     with torch.cuda.device(angles.device):
-        rc = lib.brdf_hip_fit_channels_dev(method, model, angles.data_ptr(), x.data_ptr(), n, n, K, _dptr(p), _dptr(lba), _dptr(uba),
+        rc = lib.brdf_hip_fit_channels_dev(method, model, angles.data_ptr(), x.data_ptr(), int(x_stride), n, K, _dptr(p), _dptr(lba), _dptr(uba),
                                            _dptr(dsa), itmax, _dptr(oa), _dptr(info), _dptr(covar), _stream_handle(torch))
     out = []
     for c in range(K):
@@ -407,6 +414,18 @@ def last_packed_stats() -> list:
     while lib.brdf_hip_last_packed_stats(len(out), C.byref(fits), C.byref(stride), C.byref(chunks)) == 0:
         out.append({"fits": fits.value, "stride": stride.value, "chunks": chunks.value})
     return out
+
+
+BATCH_KERNELS = ("lane", "rows", "wave", "workgroup", "eight-wave", "512x8", "weighted lane")  # brdf_hip_last_batch_launch's codes
+
+
+def last_batch_launch() -> dict | None:
+    """the kernel this thread's last batched launch chose (brdf_hip_last_batch_launch): its code 0..6 (BATCH_KERNELS), the waves per
+    SIMD of the chosen instance, the workgroups launched and the lane scheduler's quorum / maxwait; None before the first batch"""
+    kernel, waves, grid, quorum, maxwait = C.c_int(-1), C.c_int(0), C.c_longlong(0), C.c_int(0), C.c_int(0)
+    if lib.brdf_hip_last_batch_launch(C.byref(kernel), C.byref(waves), C.byref(grid), C.byref(quorum), C.byref(maxwait)) != 0:
+        return None
+    return {"kernel": kernel.value, "waves_per_simd": waves.value, "grid": grid.value, "quorum": quorum.value, "maxwait": maxwait.value}
 
 
 def fit_batch_multi(method: int, model: int, angles, x, p0, *, devices=None, lb=None, ub=None, itmax=100, opts=None):

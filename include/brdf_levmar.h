@@ -369,6 +369,13 @@ int brdf_hip_fit_stats_batch_packed(int method, int model, const double *angles,
 /* class cls (0: <= 16 samples ... 4: <= 4096, 5: above) of the calling thread's last packed call: its fits, the row stride of its
  * launches (0 for an empty class; class 5: the largest count) and its chunks (class 5: one run per fit).  LM_ERROR for another cls. */
 int brdf_hip_last_packed_stats(int cls, long long *fits, int *stride, int *chunks);
+/* The kernel the calling thread's last batched launch chose (uniform, ragged, weighted, or one class of a packed call), so that a
+ * caller who sets a tuning switch can see that it was obeyed.  *kernel: 0 one lane per fit, 1 four fits per wave, 2 one wave per fit,
+ * 3 one workgroup per fit, 4 eight waves per fit, 5 the 512 x 8 geometry (BRDF_HIP_BATCH_BIG=0), 6 one lane per weighted fit;
+ * *waves_per_simd: the chosen instance's launch bound (kernels 0 and 6: BRDF_HIP_LANE_WAVES; 0 where the kernel states none);
+ * *grid: workgroups launched; *quorum, *maxwait: BRDF_HIP_LANE_QUORUM / _MAXWAIT as kernels 0 and 6 received them (0 elsewhere).
+ * Any pointer may be NULL.  LM_ERROR while the thread has launched no batch. */
+int brdf_hip_last_batch_launch(int *kernel, int *waves_per_simd, long long *grid, int *quorum, int *maxwait);
 
 /* hx[i] = model(p; sample i) for device-resident planes; d_hx DEVICE pointer, p HOST pointer. */
 int brdf_hip_model_eval_dev(int model, const double *d_angles, int n, const double *p, double *d_hx,

@@ -19,13 +19,29 @@ def _declared_symbols():
 def test_header_symbols_are_exported():
     import brdf_amd
     declared = _declared_symbols()
-    assert {"dlevmar_dif", "dlevmar_bc_dif", "BRDFFunc_hip", "brdf_hip_fit_dev", "brdf_hip_fit_batch_dev"} <= set(declared)
+    assert {"dlevmar_dif", "dlevmar_bc_dif", "BRDFFunc_hip", "brdf_hip_fit_dev", "brdf_hip_fit_batch_dev", "brdf_hip_last_batch_launch"} <= set(declared)
     lib = C.CDLL(brdf_amd.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/brdf_levmar.h but not exported"
     # and the Python binding table covers exactly the header
     from brdf_amd._lib import ABI
     assert sorted(ABI) == declared
+
+
+def test_last_batch_launch_takes_null_pointers_and_says_when_there_was_none():
+    """brdf_hip_last_batch_launch: LM_ERROR and kernel -1 exactly while the calling thread has launched no batch; any pointer may be null"""
+    import threading
+    import brdf_amd
+    from brdf_amd._lib import lib
+    seen = []
+    t = threading.Thread(target=lambda: seen.append((lib.brdf_hip_last_batch_launch(None, None, None, None, None), brdf_amd.last_batch_launch())))
+    t.start()
+    t.join()
+    assert seen == [(-1, None)]  # a fresh thread: the record is per thread
+    kernel = C.c_int(7)
+    rc = lib.brdf_hip_last_batch_launch(C.byref(kernel), None, None, None, None)
+    assert (rc, kernel.value) == (-1, -1) or (rc == 0 and 0 <= kernel.value <= 6)
+    assert (brdf_amd.last_batch_launch() is None) == (rc == -1)
 
 
 def test_library_is_self_contained_hip_code():
