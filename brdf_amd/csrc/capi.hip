@@ -16,6 +16,7 @@
 
 #include "../../include/brdf_levmar.h"
 #include "batch_fit.h"
+#include "capture_fit.h"
 #include "fit_host.h"
 #include "fit_stats.h"
 #include "packed_fit.h"
@@ -733,13 +734,18 @@ int brdf_hip_cosines_dev(const double *d_vertices, const int *d_faces, const dou
 
 void brdf_hip_led_table(double *leds16x3) { led_table(leds16x3); }
 
+// the capture entries (capture_fit.h): what all seven take, in the order of CaptureArgs
+#define CAPTURE_ARGS \
+  {model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin, rv_mode, p0, lb, ub, itmax, opts, \
+   static_cast<hipStream_t>(stream)}
+
 int brdf_hip_fit_capture_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
                              const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf,
                              const double *leds, const double *view_origin, int rv_mode, const double *p0, const double *lb,
                              const double *ub, int itmax, const double *opts, double *d_brdf_surfaces, double *avg,
                              long long *n_pixels, void *stream) {
-  return capture_fit_run(model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin,
-                         rv_mode, p0, lb, ub, itmax, opts, d_brdf_surfaces, avg, n_pixels, static_cast<hipStream_t>(stream));
+  const CaptureFitArgs a = {CAPTURE_ARGS, d_brdf_surfaces, avg, n_pixels, nullptr, nullptr, nullptr, nullptr};
+  return capture_fit_run(a);
 }
 
 int brdf_hip_fit_capture_stats_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
@@ -748,9 +754,8 @@ int brdf_hip_fit_capture_stats_dev(int model, const unsigned char *d_images, int
                                    const double *lb, const double *ub, int itmax, const double *opts, double *d_brdf_surfaces,
                                    double *avg, long long *n_pixels, void *stream, double *d_surface_covar,
                                    double *d_surface_stats, int *d_surface_rank) {
-  return capture_fit_run(model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin,
-                         rv_mode, p0, lb, ub, itmax, opts, d_brdf_surfaces, avg, n_pixels, static_cast<hipStream_t>(stream),
-                         d_surface_covar, d_surface_stats, d_surface_rank);
+  const CaptureFitArgs a = {CAPTURE_ARGS, d_brdf_surfaces, avg, n_pixels, d_surface_covar, d_surface_stats, d_surface_rank, nullptr};
+  return capture_fit_run(a);
 }
 
 int brdf_hip_fit_capture_masked_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
@@ -761,9 +766,8 @@ int brdf_hip_fit_capture_masked_dev(int model, const unsigned char *d_images, in
                                     double *d_surface_stats, int *d_surface_rank, int v_min, int v_max, double cos_min,
                                     int *d_surface_count) {
   const CaptureMask mask = {v_min, v_max, cos_min, d_surface_count};
-  return capture_fit_run(model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin,
-                         rv_mode, p0, lb, ub, itmax, opts, d_brdf_surfaces, avg, n_pixels, static_cast<hipStream_t>(stream),
-                         d_surface_covar, d_surface_stats, d_surface_rank, &mask);
+  const CaptureFitArgs a = {CAPTURE_ARGS, d_brdf_surfaces, avg, n_pixels, d_surface_covar, d_surface_stats, d_surface_rank, &mask};
+  return capture_fit_run(a);
 }
 
 int brdf_hip_fit_capture_faces_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
@@ -773,9 +777,8 @@ int brdf_hip_fit_capture_faces_dev(int model, const unsigned char *d_images, int
                                    double *d_brdf_surfaces, double *d_surface_info, int *d_surface_ret, double *d_surface_covar,
                                    double *d_surface_stats, int *d_surface_rank, int *d_surface_count, int *d_face_pixels, double *avg,
                                    long long *n_pixels, long long *n_faces, void *stream) {
-  const CaptureFacesArgs a = {model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin, rv_mode, p0, lb, ub,
-                              itmax, opts, v_min, v_max, cos_min, workspace_bytes, d_brdf_surfaces, d_surface_info, d_surface_ret, d_surface_covar,
-                              d_surface_stats, d_surface_rank, d_surface_count, d_face_pixels, avg, n_pixels, n_faces, static_cast<hipStream_t>(stream)};
+  const CaptureFacesArgs a = {{CAPTURE_ARGS, v_min, v_max, cos_min, d_face_pixels, n_pixels, n_faces}, workspace_bytes, d_brdf_surfaces, d_surface_info,
+                              d_surface_ret, d_surface_covar, d_surface_stats, d_surface_rank, d_surface_count, avg};
   return capture_faces_run(a);
 }
 
@@ -785,9 +788,8 @@ int brdf_hip_fit_capture_means_dev(int model, const unsigned char *d_images, int
                                    const double *opts, int v_min, int v_max, double cos_min, double *d_brdf_surfaces, double *d_surface_info,
                                    int *d_surface_ret, double *d_surface_covar, double *d_surface_stats, int *d_surface_rank, int *d_surface_count,
                                    int *d_surface_lights, int *d_face_pixels, double *avg, long long *n_pixels, long long *n_faces, void *stream) {
-  const CaptureMeansArgs a = {{model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin, rv_mode, p0, lb, ub,
-                               itmax, opts, v_min, v_max, cos_min, 0, d_brdf_surfaces, d_surface_info, d_surface_ret, d_surface_covar,
-                               d_surface_stats, d_surface_rank, d_surface_count, d_face_pixels, avg, n_pixels, n_faces, static_cast<hipStream_t>(stream)},
+  const CaptureMeansArgs a = {{{CAPTURE_ARGS, v_min, v_max, cos_min, d_face_pixels, n_pixels, n_faces}, 0, d_brdf_surfaces, d_surface_info, d_surface_ret,
+                               d_surface_covar, d_surface_stats, d_surface_rank, d_surface_count, avg},
                               d_surface_lights};
   return capture_means_run(a);
 }
@@ -797,8 +799,8 @@ int brdf_hip_fit_capture_single_dev(int model, const unsigned char *d_images, in
                                     const double *leds, const double *view_origin, int rv_mode, const double *p0,
                                     const double *lb, const double *ub, int itmax, const double *opts, double *single_brdf,
                                     double *info, long long *n_faces_used, void *stream) {
-  return capture_fit_single_run(model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin,
-                                rv_mode, p0, lb, ub, itmax, opts, single_brdf, info, n_faces_used, static_cast<hipStream_t>(stream));
+  const CaptureSingleArgs a = {CAPTURE_ARGS, single_brdf, info, n_faces_used};
+  return capture_fit_single_run(a);
 }
 
 int brdf_hip_fit_capture_single_faces_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
@@ -807,21 +809,12 @@ int brdf_hip_fit_capture_single_faces_dev(int model, const unsigned char *d_imag
                                           const double *opts, int v_min, int v_max, double cos_min, double *single_brdf, double *info, int *ret,
                                           double *covar, double *stats, int *rank, long long *count, double *d_face_sumsq, int *d_face_count,
                                           int *d_face_pixels, long long *n_pixels, long long *n_faces, void *stream) {
-  CaptureSingleFacesArgs a = {};
-  a.cap = {model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin, rv_mode, p0, lb, ub,
-           itmax, opts, v_min, v_max, cos_min, 0, nullptr, nullptr, nullptr, nullptr,
-           nullptr, nullptr, nullptr, d_face_pixels, nullptr, n_pixels, n_faces, static_cast<hipStream_t>(stream)};
-  a.single_brdf = single_brdf;
-  a.info = info;
-  a.ret = ret;
-  a.covar = covar;
-  a.stats = stats;
-  a.rank = rank;
-  a.count = count;
-  a.d_face_sumsq = d_face_sumsq;
-  a.d_face_count = d_face_count;
+  const CaptureSingleFacesArgs a = {{CAPTURE_ARGS, v_min, v_max, cos_min, d_face_pixels, n_pixels, n_faces}, single_brdf, info, ret, covar, stats, rank,
+                                    count, d_face_sumsq, d_face_count};
   return capture_single_faces_run(a);
 }
+
+#undef CAPTURE_ARGS
 
 int brdf_hip_device_count(void) {
   int c = 0;

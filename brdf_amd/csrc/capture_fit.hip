@@ -15,37 +15,17 @@
 //   store     brdf_surfaces[face][channel] <- the fit of the face's last pixel; sums of kd, ks, n over all fits
 //
 // Everything stays in HBM between the steps; the host sees S and the three averages.
-#include <cstdio>
 #include <vector>
 
 #include "../../include/brdf_levmar.h"
-#include "capture_compact.h"
-#include "fit_host.h"
+#include "capture_group.h"
 #include "fit_stats.h"
 
 namespace brdf {
 
 namespace {
 
-// (kCT, face_of and count_kernel, pass 1 of the compaction: capture_compact.h)
-__global__ __launch_bounds__(kCT) void compact_kernel(const int *pm, int H, int W, int nf, const long long *block_offset,
-                                                      long long *pixel_of, int *face_of_surfel, long long *last_of_face) {
-  __shared__ int wave_cnt[kCT / 64];
-  const long long g = (long long)blockIdx.x * kCT + threadIdx.x;
-  const int f = (g < (long long)H * W) ? face_of(pm, H, W, g) : -1;
-  const bool valid = f > -1 && f < nf;
-  const unsigned long long m = __ballot(valid);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) wave_cnt[wave] = __popcll(m);
-  __syncthreads();
-  if (!valid) return;
-  long long s = block_offset[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-  for (int w = 0; w < wave; ++w) s += wave_cnt[w];
-  pixel_of[s] = g;
-  face_of_surfel[s] = f;
-  atomicMax(reinterpret_cast<unsigned long long *>(last_of_face) + f, (unsigned long long)(s + 1));  // 0 = no pixel
-}
-
+// (the compaction and the face's last pixel: capture_group.hip, FaceStat::kLastPixel)
 // fit id q = 3 s + c: the three channels of pixel s are consecutive, as in the reference's loop nest
 __global__ __launch_bounds__(kCT) void gather_kernel(const unsigned char *images, int L, int H, int W, const long long *pixel_of,
                                                      const int *face_of_surfel, long long S, const double *p0, double *x,
@@ -72,7 +52,6 @@ __global__ __launch_bounds__(kCT) void gather_kernel(const unsigned char *images
 // brdf_surfaces(face, channel) <- the last pixel's fit; per-block partial sums of kd, ks, n in a fixed order
 __global__ __launch_bounds__(kCT) void store_kernel(const double *p, const int *face_of_surfel, const long long *last_of_face,
                                                     long long S, double *brdf_surfaces, double *block_sums) {
-  __shared__ double red[3][kCT];
   const long long q = (long long)blockIdx.x * kCT + threadIdx.x;
   double v[3] = {0.0, 0.0, 0.0};
   if (q < 3 * S) {
@@ -89,14 +68,7 @@ __global__ __launch_bounds__(kCT) void store_kernel(const double *p, const int *
       dst[2] = v[2];
     }
   }
-  for (int k = 0; k < 3; ++k) red[k][threadIdx.x] = v[k];
-  __syncthreads();
-  for (int w = kCT / 2; w > 0; w >>= 1) {
-    if (threadIdx.x < w)
-      for (int k = 0; k < 3; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x < 3) block_sums[(size_t)blockIdx.x * 3 + threadIdx.x] = red[threadIdx.x][0];
+  block_sums3(v, block_sums);
 }
 
 // the optional statistics tail: row (face, channel) of the three maps reads the fit store_kernel's rule picks for it -- channel c
@@ -222,32 +194,21 @@ __global__ __launch_bounds__(kCT) void single_pack_kernel(const unsigned char *i
   }
 }
 
-using DevBuf = DeviceBlock<char>;  // scoped: bytes
-
-#define CAP_OK(call)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (call);                                                               \
-    if (e_ != hipSuccess) {                                                               \
-      set_error("brdf_hip_fit_capture_dev(): %s failed: %s", #call, hipGetErrorString(e_)); \
-      return kLmError;                                                                    \
-    }                                                                                     \
-  } while (0)
-
 }  // namespace
 
-int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
-                    const double *d_vertices, const int *d_faces, const double *d_normals, int nf, const double *leds,
-                    const double *view, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
-                    const double *opts, double *d_brdf_surfaces, double *avg, long long *n_pixels, hipStream_t stream,
-                    double *d_surface_covar, double *d_surface_stats, int *d_surface_rank, const CaptureMask *mask) {
-  const bool want_stats = d_surface_covar || d_surface_stats || d_surface_rank;
+int capture_fit_run(const CaptureFitArgs &fa) {
+  const CaptureArgs &a = fa.cap;
+  const CaptureMask *mask = fa.mask;
+  const int model = a.model, L = a.L, nf = a.nf;
+  hipStream_t stream = a.stream;
+  const bool want_stats = fa.d_surface_covar || fa.d_surface_stats || fa.d_surface_rank;
   const char *who = mask ? "brdf_hip_fit_capture_masked_dev" : (want_stats ? "brdf_hip_fit_capture_stats_dev" : "brdf_hip_fit_capture_dev");
   if (mask && (mask->v_min > mask->v_max || mask->cos_min != mask->cos_min || model < 0 || model >= MODEL_COUNT)) {
     set_error("%s(): bad validity rule (v_min %d > v_max %d, or cos_min not a number) or unknown model %d", who, mask->v_min, mask->v_max, model);
     return kLmError;
   }
-  if (!d_images || !d_pixel_map || !d_vertices || !d_faces || !d_normals || !leds || !view || !p0 || !d_brdf_surfaces ||
-      L <= 0 || L > 64 || H <= 0 || W <= 0 || nf <= 0) {
+  if (!a.d_images || !a.d_pixel_map || !a.d_vertices || !a.d_faces || !a.d_normals || !a.leds || !a.view || !a.p0 || !fa.d_brdf_surfaces ||
+      L <= 0 || L > 64 || a.H <= 0 || a.W <= 0 || nf <= 0) {
     set_error("%s(): bad arguments", who);
     return kLmError;
   }
@@ -256,96 +217,75 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
     return kLmError;
   }
   (void)hipGetLastError();
-  const long long npx = (long long)H * W;
-  const int nb = (int)((npx + kCT - 1) / kCT);
-  DevBuf counts, offsets, last;
-  CAP_OK(counts.ensure(sizeof(int) * nb));
-  CAP_OK(offsets.ensure(sizeof(long long) * nb));
-  CAP_OK(last.ensure(sizeof(long long) * nf));
-  CAP_OK(hipMemsetAsync(last.ptr, 0, sizeof(long long) * nf, stream));
-  hipLaunchKernelGGL(count_kernel, dim3(nb), dim3(kCT), 0, stream, d_pixel_map, H, W, nf, counts.as<int>());
-  std::vector<int> h_counts(nb);
-  CAP_OK(hipMemcpyAsync(h_counts.data(), counts.ptr, sizeof(int) * nb, hipMemcpyDeviceToHost, stream));
-  CAP_OK(hipStreamSynchronize(stream));
-  std::vector<long long> h_off(nb);
-  long long S = 0;
-  for (int b = 0; b < nb; ++b) {
-    h_off[b] = S;
-    S += h_counts[b];
-  }
-  if (n_pixels) *n_pixels = S;
-  if (avg) avg[0] = avg[1] = avg[2] = 0.0;
+  DevBuf last;
+  CAPTURE_OK(who, last.ensure(sizeof(long long) * nf));
+  CAPTURE_OK(who, hipMemsetAsync(last.ptr, 0, sizeof(long long) * nf, stream));
+  PixelCompaction walk;
+  walk.stat = FaceStat::kLastPixel;
+  walk.d_face_stat = last.ptr;
+  walk.max_S = 0x7fffffffLL / 3;  // 3 S fits
+  if (capture_compact_run(who, a, walk) != 0) return kLmError;
+  const long long S = walk.S;
+  if (fa.n_pixels) *fa.n_pixels = S;
+  if (fa.avg) fa.avg[0] = fa.avg[1] = fa.avg[2] = 0.0;
   if (S == 0) return 0;
-  if (3 * S > 0x7fffffffLL) {
+  if (S > walk.max_S) {
     set_error("%s(): %lld pixels carry a face; the batched fitter takes at most 2^31-1 fits per call", who, S);
     return kLmError;
   }
-  CAP_OK(hipMemcpyAsync(offsets.ptr, h_off.data(), sizeof(long long) * nb, hipMemcpyHostToDevice, stream));
-  DevBuf pixel_of, face_s, faces3, x, p, angles, ret, p0d, sums;
-  CAP_OK(pixel_of.ensure(sizeof(long long) * S));
-  CAP_OK(face_s.ensure(sizeof(int) * S));
-  CAP_OK(faces3.ensure(sizeof(int) * 3 * S));
-  CAP_OK(x.ensure(sizeof(double) * 3 * S * L));
-  CAP_OK(p.ensure(sizeof(double) * 9 * S));
-  CAP_OK(angles.ensure(sizeof(double) * 9 * S * L));
-  CAP_OK(ret.ensure(sizeof(int) * 3 * S));
-  CAP_OK(p0d.ensure(sizeof(double) * 3));
-  CAP_OK(hipMemcpyAsync(p0d.ptr, p0, sizeof(double) * 3, hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(compact_kernel, dim3(nb), dim3(kCT), 0, stream, d_pixel_map, H, W, nf, offsets.as<long long>(),
-                     pixel_of.as<long long>(), face_s.as<int>(), last.as<long long>());
+  DevBuf &pixel_of = walk.pixel_of, &face_s = walk.face_s;
+  DevBuf faces3, x, p, angles, ret, p0d, sums;
+  CAPTURE_OK(who, faces3.ensure(sizeof(int) * 3 * S));
+  CAPTURE_OK(who, x.ensure(sizeof(double) * 3 * S * L));
+  CAPTURE_OK(who, p.ensure(sizeof(double) * 9 * S));
+  CAPTURE_OK(who, angles.ensure(sizeof(double) * 9 * S * L));
+  CAPTURE_OK(who, ret.ensure(sizeof(int) * 3 * S));
+  CAPTURE_OK(who, p0d.ensure(sizeof(double) * 3));
+  CAPTURE_OK(who, hipMemcpyAsync(p0d.ptr, a.p0, sizeof(double) * 3, hipMemcpyHostToDevice, stream));
   long long gb = (3 * S * L + kCT - 1) / kCT;
   if (gb > 256 * 64) gb = 256 * 64;
-  hipLaunchKernelGGL(gather_kernel, dim3((unsigned)gb), dim3(kCT), 0, stream, d_images, L, H, W, pixel_of.as<long long>(),
+  hipLaunchKernelGGL(gather_kernel, dim3((unsigned)gb), dim3(kCT), 0, stream, a.d_images, L, a.H, a.W, pixel_of.as<long long>(),
                      face_s.as<int>(), S, p0d.as<double>(), x.as<double>(), faces3.as<int>(), p.as<double>());
-  CAP_OK(hipGetLastError());
-  if (cosines_run(d_vertices, d_faces, d_normals, faces3.as<int>(), 3 * S, leds, L, view, rv_mode, angles.as<double>(), stream) != 0)
+  CAPTURE_OK(who, hipGetLastError());
+  if (cosines_run(a.d_vertices, a.d_faces, a.d_normals, faces3.as<int>(), 3 * S, a.leds, L, a.view, a.rv_mode, angles.as<double>(), stream) != 0)
     return kLmError;
   DevBuf fit_counts;
   if (mask) {  // valid samples to the front of every fit's rows, in place; the fits below are ragged
     const long long Q = 3 * S;
     const int use1 = model != MODEL_PHONG, use2 = model != MODEL_BLINN_PHONG;  // the planes the model reads (brdf_models.h: uses_c1, uses_c2)
-    CAP_OK(fit_counts.ensure(sizeof(int) * Q));
+    CAPTURE_OK(who, fit_counts.ensure(sizeof(int) * Q));
     if (L == 16)
       hipLaunchKernelGGL(mask_rows16_kernel, dim3((unsigned)((Q * 16 + kCT - 1) / kCT)), dim3(kCT), 0, stream, angles.as<double>(), x.as<double>(), Q,
                          mask->v_min, mask->v_max, mask->cos_min, use1, use2, fit_counts.as<int>());
     else
       hipLaunchKernelGGL(mask_serial_kernel, dim3((unsigned)((Q + kCT - 1) / kCT)), dim3(kCT), 0, stream, angles.as<double>(), x.as<double>(), Q, L,
                          mask->v_min, mask->v_max, mask->cos_min, use1, use2, fit_counts.as<int>());
-    CAP_OK(hipGetLastError());
+    CAPTURE_OK(who, hipGetLastError());
   }
   // dlevmar_bc_dif: brdfdata.cpp:1119; no info; with a mask the fits are ragged
-  const BatchFitArgs a = {BRDF_METHOD_BC_DIF, model, angles.as<double>(), x.as<double>(), (int)(3 * S), L, p.as<double>(), lb, ub, itmax, opts, nullptr,
-                          ret.as<int>(), stream, mask ? fit_counts.as<int>() : nullptr};
-  if (batch_fit_enqueue(a, who) != 0) return kLmError;
+  const BatchFitArgs b = {BRDF_METHOD_BC_DIF, model, angles.as<double>(), x.as<double>(), (int)(3 * S), L, p.as<double>(), a.lb, a.ub, a.itmax, a.opts,
+                          nullptr, ret.as<int>(), stream, mask ? fit_counts.as<int>() : nullptr};
+  if (batch_fit_enqueue(b, who) != 0) return kLmError;
   const int sb = (int)((3 * S + kCT - 1) / kCT);
-  CAP_OK(sums.ensure(sizeof(double) * 3 * sb));
+  CAPTURE_OK(who, sums.ensure(sizeof(double) * 3 * sb));
   hipLaunchKernelGGL(store_kernel, dim3(sb), dim3(kCT), 0, stream, p.as<double>(), face_s.as<int>(), last.as<long long>(), S,
-                     d_brdf_surfaces, sums.as<double>());
-  CAP_OK(hipGetLastError());
+                     fa.d_brdf_surfaces, sums.as<double>());
+  CAPTURE_OK(who, hipGetLastError());
   if (mask && mask->d_surface_count) {
     hipLaunchKernelGGL(count_map_kernel, dim3((3 * nf + kCT - 1) / kCT), dim3(kCT), 0, stream, last.as<long long>(), nf, fit_counts.as<int>(),
                        mask->d_surface_count);
-    CAP_OK(hipGetLastError());
+    CAPTURE_OK(who, hipGetLastError());
   }
   DevBuf src_of_row;
   if (want_stats) {  // the staged angles / x / p are still in HBM: one pass over the stored fits
-    CAP_OK(src_of_row.ensure(sizeof(int) * 3 * (size_t)nf));
+    CAPTURE_OK(who, src_of_row.ensure(sizeof(int) * 3 * (size_t)nf));
     hipLaunchKernelGGL(stats_rows_kernel, dim3((3 * nf + kCT - 1) / kCT), dim3(kCT), 0, stream, last.as<long long>(), nf, src_of_row.as<int>());
-    CAP_OK(hipGetLastError());
-    const FitStatsArgs fs = {a.method, model, a.d_angles, a.d_x, a.S, L, a.d_p, opts, d_surface_covar, d_surface_stats, d_surface_rank,
-                             src_of_row.as<int>(), 3 * nf, stream, a.d_counts};
+    CAPTURE_OK(who, hipGetLastError());
+    const FitStatsArgs fs = {b.method, model, b.d_angles, b.d_x, b.S, L, b.d_p, a.opts, fa.d_surface_covar, fa.d_surface_stats, fa.d_surface_rank,
+                             src_of_row.as<int>(), 3 * nf, stream, b.d_counts};
     if (fit_stats_enqueue(fs, who) != 0) return kLmError;
   }
-  std::vector<double> h_sums((size_t)3 * sb);
-  CAP_OK(hipMemcpyAsync(h_sums.data(), sums.ptr, sizeof(double) * 3 * sb, hipMemcpyDeviceToHost, stream));
-  CAP_OK(hipStreamSynchronize(stream));
-  if (avg) {
-    double t[3] = {0.0, 0.0, 0.0};
-    for (int b = 0; b < sb; ++b)
-      for (int k = 0; k < 3; ++k) t[k] += h_sums[(size_t)3 * b + k];
-    for (int k = 0; k < 3; ++k) avg[k] = t[k] / ((double)nf * 3);  // "avg_kd/(m_faces.rows()*3)", brdfdata.cpp:1224-1226
-  }
-  return 0;
+  return capture_average(who, a, sums.as<double>(), sb, fa.avg);
 }
 
 
@@ -354,88 +294,75 @@ int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int 
 // reference fills phi/thetaDash/theta/I only for the faces some pixel carries and leaves the other rows of its
 // matrices uninitialised, then pairs x (face-major) with planes read through a column-major linear index (:1031): both
 // slips are not reproduced -- the fit sees exactly the carried faces, samples and measurements paired.
-int capture_fit_single_run(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
-                           const double *d_vertices, const int *d_faces, const double *d_normals, int nf, const double *leds,
-                           const double *view, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
-                           const double *opts, double *single_brdf, double *info, long long *n_faces_used, hipStream_t stream) {
-  if (!d_images || !d_pixel_map || !d_vertices || !d_faces || !d_normals || !leds || !view || !p0 || !single_brdf || L <= 0 ||
-      L > 64 || H <= 0 || W <= 0 || nf <= 0) {
-    set_error("brdf_hip_fit_capture_single_dev(): bad arguments");
+int capture_fit_single_run(const CaptureSingleArgs &sa) {
+  static const char *const who = "brdf_hip_fit_capture_single_dev";
+  const CaptureArgs &a = sa.cap;
+  const int L = a.L, nf = a.nf;
+  hipStream_t stream = a.stream;
+  if (!a.d_images || !a.d_pixel_map || !a.d_vertices || !a.d_faces || !a.d_normals || !a.leds || !a.view || !a.p0 || !sa.single_brdf || L <= 0 ||
+      L > 64 || a.H <= 0 || a.W <= 0 || nf <= 0) {
+    set_error("%s(): bad arguments", who);
     return kLmError;
   }
   (void)hipGetLastError();
-  const long long npx = (long long)H * W;
-  const int nb = (int)((npx + kCT - 1) / kCT), fb = (nf + kCT - 1) / kCT;
-  DevBuf counts, offsets, last, fcounts, foffsets;
-  CAP_OK(counts.ensure(sizeof(int) * nb));
-  CAP_OK(offsets.ensure(sizeof(long long) * nb));
-  CAP_OK(last.ensure(sizeof(long long) * nf));
-  CAP_OK(fcounts.ensure(sizeof(int) * fb));
-  CAP_OK(foffsets.ensure(sizeof(long long) * fb));
-  CAP_OK(hipMemsetAsync(last.ptr, 0, sizeof(long long) * nf, stream));
-  hipLaunchKernelGGL(count_kernel, dim3(nb), dim3(kCT), 0, stream, d_pixel_map, H, W, nf, counts.as<int>());
-  std::vector<int> h_counts(nb);
-  CAP_OK(hipMemcpyAsync(h_counts.data(), counts.ptr, sizeof(int) * nb, hipMemcpyDeviceToHost, stream));
-  CAP_OK(hipStreamSynchronize(stream));
-  std::vector<long long> h_off(nb);
-  long long S = 0;
-  for (int b = 0; b < nb; ++b) {
-    h_off[b] = S;
-    S += h_counts[b];
-  }
-  if (n_faces_used) *n_faces_used = 0;
-  if (S == 0) {
-    set_error("brdf_hip_fit_capture_single_dev(): no pixel carries a face");
+  const int fb = (nf + kCT - 1) / kCT;
+  DevBuf last, fcounts, foffsets;
+  CAPTURE_OK(who, last.ensure(sizeof(long long) * nf));
+  CAPTURE_OK(who, fcounts.ensure(sizeof(int) * fb));
+  CAPTURE_OK(who, foffsets.ensure(sizeof(long long) * fb));
+  CAPTURE_OK(who, hipMemsetAsync(last.ptr, 0, sizeof(long long) * nf, stream));
+  PixelCompaction walk;
+  walk.stat = FaceStat::kLastPixel;
+  walk.d_face_stat = last.ptr;
+  walk.max_S = (long long)a.H * a.W;  // no limit of this entry's own
+  if (capture_compact_run(who, a, walk) != 0) return kLmError;
+  if (sa.n_faces_used) *sa.n_faces_used = 0;
+  if (walk.S == 0) {
+    set_error("%s(): no pixel carries a face", who);
     return kLmError;
   }
-  CAP_OK(hipMemcpyAsync(offsets.ptr, h_off.data(), sizeof(long long) * nb, hipMemcpyHostToDevice, stream));
-  DevBuf pixel_of, face_s;
-  CAP_OK(pixel_of.ensure(sizeof(long long) * S));
-  CAP_OK(face_s.ensure(sizeof(int) * S));
-  hipLaunchKernelGGL(compact_kernel, dim3(nb), dim3(kCT), 0, stream, d_pixel_map, H, W, nf, offsets.as<long long>(),
-                     pixel_of.as<long long>(), face_s.as<int>(), last.as<long long>());
   hipLaunchKernelGGL(face_count_kernel, dim3(fb), dim3(kCT), 0, stream, last.as<long long>(), nf, fcounts.as<int>());
   std::vector<int> h_fc(fb);
-  CAP_OK(hipMemcpyAsync(h_fc.data(), fcounts.ptr, sizeof(int) * fb, hipMemcpyDeviceToHost, stream));
-  CAP_OK(hipStreamSynchronize(stream));
+  CAPTURE_OK(who, hipMemcpyAsync(h_fc.data(), fcounts.ptr, sizeof(int) * fb, hipMemcpyDeviceToHost, stream));
+  CAPTURE_OK(who, hipStreamSynchronize(stream));
   std::vector<long long> h_fo(fb);
   long long F = 0;
   for (int b = 0; b < fb; ++b) {
     h_fo[b] = F;
     F += h_fc[b];
   }
-  if (n_faces_used) *n_faces_used = F;
+  if (sa.n_faces_used) *sa.n_faces_used = F;
   const long long n = F * L;
   if (n > 0x7fffffffLL) {
-    set_error("brdf_hip_fit_capture_single_dev(): %lld samples exceed one fit's index range", n);
+    set_error("%s(): %lld samples exceed one fit's index range", who, n);
     return kLmError;
   }
-  CAP_OK(hipMemcpyAsync(foffsets.ptr, h_fo.data(), sizeof(long long) * fb, hipMemcpyHostToDevice, stream));
+  CAPTURE_OK(who, hipMemcpyAsync(foffsets.ptr, h_fo.data(), sizeof(long long) * fb, hipMemcpyHostToDevice, stream));
   DevBuf face_list, pixel_list, angles_f, planes, x3;
-  CAP_OK(face_list.ensure(sizeof(int) * F));
-  CAP_OK(pixel_list.ensure(sizeof(long long) * F));
-  CAP_OK(angles_f.ensure(sizeof(double) * 3 * n));
-  CAP_OK(planes.ensure(sizeof(double) * 3 * n));
-  CAP_OK(x3.ensure(sizeof(double) * 3 * n));
-  hipLaunchKernelGGL(face_compact_kernel, dim3(fb), dim3(kCT), 0, stream, last.as<long long>(), pixel_of.as<long long>(), nf,
+  CAPTURE_OK(who, face_list.ensure(sizeof(int) * F));
+  CAPTURE_OK(who, pixel_list.ensure(sizeof(long long) * F));
+  CAPTURE_OK(who, angles_f.ensure(sizeof(double) * 3 * n));
+  CAPTURE_OK(who, planes.ensure(sizeof(double) * 3 * n));
+  CAPTURE_OK(who, x3.ensure(sizeof(double) * 3 * n));
+  hipLaunchKernelGGL(face_compact_kernel, dim3(fb), dim3(kCT), 0, stream, last.as<long long>(), walk.pixel_of.as<long long>(), nf,
                      foffsets.as<long long>(), face_list.as<int>(), pixel_list.as<long long>());
-  CAP_OK(hipGetLastError());
-  if (cosines_run(d_vertices, d_faces, d_normals, face_list.as<int>(), F, leds, L, view, rv_mode, angles_f.as<double>(), stream) != 0)
+  CAPTURE_OK(who, hipGetLastError());
+  if (cosines_run(a.d_vertices, a.d_faces, a.d_normals, face_list.as<int>(), F, a.leds, L, a.view, a.rv_mode, angles_f.as<double>(), stream) != 0)
     return kLmError;
   long long gb = (n + kCT - 1) / kCT;
   if (gb > 256 * 64) gb = 256 * 64;
-  hipLaunchKernelGGL(single_pack_kernel, dim3((unsigned)gb), dim3(kCT), 0, stream, d_images, L, H, W, pixel_list.as<long long>(),
+  hipLaunchKernelGGL(single_pack_kernel, dim3((unsigned)gb), dim3(kCT), 0, stream, a.d_images, L, a.H, a.W, pixel_list.as<long long>(),
                      angles_f.as<double>(), F, planes.as<double>(), x3.as<double>());
-  CAP_OK(hipGetLastError());
+  CAPTURE_OK(who, hipGetLastError());
   // "do the calculation once for each color-channel", brdfdata.cpp:1161: three dlevmar_bc_dif fits (:1058) over the SAME planes --
   // one shared resident launch where the fit fits the chip (channels_fit_impl.h), one fit after the other otherwise
   double p3[9];
   for (int c = 0; c < 3; ++c)
-    for (int k = 0; k < 3; ++k) p3[3 * c + k] = p0[k];
-  const int worst = channels_fit_run(BRDF_METHOD_BC_DIF, model, planes.as<double>(), x3.as<double>(), n, (int)n, 3, p3, lb, ub, nullptr, itmax, opts,
-                                     info, nullptr, stream);
-  for (int k = 0; k < 9; ++k) single_brdf[k] = p3[k];
-  CAP_OK(hipStreamSynchronize(stream));
+    for (int k = 0; k < 3; ++k) p3[3 * c + k] = a.p0[k];
+  const int worst = channels_fit_run(BRDF_METHOD_BC_DIF, a.model, planes.as<double>(), x3.as<double>(), n, (int)n, 3, p3, a.lb, a.ub, nullptr, a.itmax,
+                                     a.opts, sa.info, nullptr, stream);
+  for (int k = 0; k < 9; ++k) sa.single_brdf[k] = p3[k];
+  CAPTURE_OK(who, hipStreamSynchronize(stream));
   return worst;
 }
 

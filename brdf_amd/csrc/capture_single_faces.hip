@@ -3,7 +3,8 @@
 // validity rule; and, per carried face and channel, the sum of squared residuals against that one fit: where on the object the
 // one-material assumption fails.  No fit or statistics kernel of its own: stream_fit_run fits, fit_stats.hip takes the statistics.
 //
-// (compact, group and cosines are capture_group.h's, shared with capture_faces.hip and capture_means.hip)
+// (compact, group and cosines are capture_group.hip's, shared with capture_faces.hip and capture_means.hip; the candidate reader, the
+// channel compaction and the scan are capture_compact.h's, shared with capture_faces.hip)
 //   pack      the candidates of a channel are ONE flat array, t = sorted pixel * L + light (capture_faces.hip's), and a channel's
 //             samples are one stream compaction of it: ballot + popcount and block counts (pass 0), one scan, place (pass 1).  The
 //             channel totals K_c are the scan's, so ONE placing pass writes the single-fit layout -- planes [3][K_c], x [K_c] --
@@ -14,9 +15,9 @@
 //             ascending order.  A face's value depends on its samples, their order and p only; no float atomics.  The chunk of a
 //             wavefront comes from one scan of the faces' chunk counts and a binary search in it.
 //
-// The kernels here are copies, not shared text: capture_faces.hip's instances keep their registers (weighted_fit.hip tells why).
 // The two candidate passes evaluate the same rule on the same bytes, so the places of pass 1 are the counts of pass 0.
 #include <algorithm>
+#include <climits>
 #include <string>
 
 #include "../../include/brdf_levmar.h"
@@ -33,123 +34,41 @@ constexpr int kAlign = 32;   // doubles: every channel's planes and measurements
 
 // ---- count and place -------------------------------------------------------------------------------------------------------------
 struct SinglePackCtx {
-  const unsigned char *images;
-  int L, H, W;
-  const long long *pixel_sorted;  // [S]: x-major pixel index, grouped by face
-  const unsigned *face_sorted;    // [S]
-  const int *rank_of_face;        // [nf]
-  const long long *face_first;    // [F + 1]
-  const double *angles_f;         // [F][3][L]
-  long long T;                    // candidates of one channel: S * L
-  int F;
-  int v_min, v_max;
-  double cos_min;
-  int use1, use2;  // the planes the model reads besides the first (brdf_models.h: uses_c1, uses_c2)
+  CandidateCtx cand;
   int *block_count;            // [blocks][3]                                                              (pass 0 writes)
-  const long long *block_off;  // [blocks][3]: the place IN ITS CHANNEL of the block's first valid candidate  (single_scan_kernel)
+  const long long *block_off;  // [blocks][3]: the place IN ITS CHANNEL of the block's first valid candidate  (block_scan3_kernel<false>)
   long long *seg;              // [3][F + 1]: where a face's samples start in the channel                   (pass 1 writes [c][0, F))
   double *ang[3], *x[3];       // the channels' planes [3][K_c] and measurements [K_c]
   long long K[3];
 };
 
-// Candidate t = (sorted pixel, light) of all three channels: the pixel's B, G, R bytes are one read, the cosine test is the face's.
+// Candidate t = (sorted pixel, light) of all three channels (capture_compact.h: read_candidate).
 //   PASS 0  the block's number of valid candidates per channel
 //   PASS 1  the plane triple and the measurement to their place; at a face's first candidate the face's offset (the prefix there)
 template <int PASS>
 __global__ __launch_bounds__(kCT) void single_pack_faces_kernel(SinglePackCtx c) {
   __shared__ int wave_cnt[kWaves][3];
   const long long t = (long long)blockIdx.x * kCT + threadIdx.x;
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  bool valid[3] = {false, false, false};
-  int v[3] = {0, 0, 0}, i = 0, r = 0;
-  long long s = 0;
-  double c0 = 0.0, c1 = 0.0, c2 = 0.0;
-  if (t < c.T) {
-    s = t / c.L;
-    i = (int)(t - s * c.L);
-    r = c.rank_of_face[c.face_sorted[s]];
-    const long long g = c.pixel_sorted[s];
-    const int px = (int)(g / c.H), py = (int)(g % c.H);
-    const unsigned char *pxl = c.images + (((size_t)i * c.H + (size_t)(c.H - 1 - py)) * c.W + px) * 3;
-    const double *a = c.angles_f + (size_t)r * 3 * c.L + i;
-    c0 = a[0];
-    c1 = a[c.L];
-    c2 = a[2 * c.L];
-    const bool cos_ok = c0 > c.cos_min && (!c.use1 || c1 > c.cos_min) && (!c.use2 || c2 > c.cos_min);  // (a NaN is not valid)
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      v[ch] = pxl[ch];
-      valid[ch] = cos_ok && v[ch] >= c.v_min && v[ch] <= c.v_max;
-    }
-  }
-  int before[3];
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const unsigned long long m = __ballot(valid[ch]);
-    before[ch] = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_cnt[wave][ch] = __popcll(m);
-  }
-  __syncthreads();
+  const Candidate k = read_candidate(c.cand, t);
+  ChannelPlaces pl = {wave_cnt};
+  pl.place(k.valid);
   if (PASS == 0) {
-    if (threadIdx.x < 3) {
-      int n = 0;
-      for (int w = 0; w < kWaves; ++w) n += wave_cnt[w][threadIdx.x];
-      c.block_count[(size_t)blockIdx.x * 3 + threadIdx.x] = n;
-    }
+    if (threadIdx.x < 3) c.block_count[(size_t)blockIdx.x * 3 + threadIdx.x] = pl.count(threadIdx.x);
     return;
   }
-  if (t >= c.T) return;
-  const bool first_of_face = i == 0 && s == c.face_first[r];
+  if (t >= c.cand.T) return;
+  const bool first_of_face = k.i == 0 && k.s == c.cand.face_first[k.r];
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) {
-    long long at = c.block_off[(size_t)blockIdx.x * 3 + ch] + before[ch];
-    for (int w = 0; w < wave; ++w) at += wave_cnt[w][ch];
-    if (first_of_face) c.seg[(size_t)ch * (c.F + 1) + r] = at;
-    if (valid[ch]) {  // (at < K[ch]: the rule of pass 0 on the same bytes)
-      const long long k = c.K[ch];
+    const long long at = pl.at(ch, c.block_off[(size_t)blockIdx.x * 3 + ch]);
+    if (first_of_face) c.seg[(size_t)ch * (c.cand.F + 1) + k.r] = at;
+    if (k.valid[ch]) {  // (at < K[ch]: the rule of pass 0 on the same bytes)
+      const long long n = c.K[ch];
       double *dst = c.ang[ch] + at;
-      dst[0] = c0;
-      dst[k] = c1;
-      dst[2 * k] = c2;
-      c.x[ch][at] = v[ch] / 255.0;  // "intensity.val[colorChannel]/255.0", brdfdata.cpp:956
-    }
-  }
-}
-
-// the scan between the two passes, one workgroup: block_count[b][ch] -> block_off[b][ch], every channel from 0; totals[ch] = K_ch, also
-// the end of the channel's face offsets, seg[ch][F]
-__global__ __launch_bounds__(kCT) void single_scan_kernel(const int *__restrict__ block_count, long long nb, long long *__restrict__ block_off,
-                                                          long long *__restrict__ seg, int F, long long *__restrict__ totals) {
-  __shared__ long long part[kCT][3];
-  const int t = threadIdx.x;
-  const long long per = (nb + kCT - 1) / kCT;
-  const long long b0 = t * per < nb ? t * per : nb, b1 = b0 + per < nb ? b0 + per : nb;
-  long long sum[3] = {0, 0, 0};
-  for (long long b = b0; b < b1; ++b) {
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) sum[ch] += block_count[b * 3 + ch];
-  }
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) part[t][ch] = sum[ch];
-  __syncthreads();
-  if (t < 3) {
-    long long run = 0;
-    for (int i = 0; i < kCT; ++i) {
-      const long long v = part[i][t];
-      part[i][t] = run;
-      run += v;
-    }
-    totals[t] = run;
-    seg[(size_t)t * (F + 1) + F] = run;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) sum[ch] = part[t][ch];
-  for (long long b = b0; b < b1; ++b) {
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      block_off[b * 3 + ch] = sum[ch];
-      sum[ch] += block_count[b * 3 + ch];
+      dst[0] = k.c0;
+      dst[n] = k.c1;
+      dst[2 * n] = k.c2;
+      c.x[ch][at] = k.v[ch] / 255.0;  // "intensity.val[colorChannel]/255.0", brdfdata.cpp:956
     }
   }
 }
@@ -261,41 +180,9 @@ ResidKernel resid_kernel_of(int model) {
   return t[model];
 }
 
-#define SINGLE_OK(call)                                                       \
-  do {                                                                        \
-    hipError_t e_ = (call);                                                   \
-    if (e_ != hipSuccess) {                                                   \
-      set_error("%s(): %s failed: %s", kWho, #call, hipGetErrorString(e_));   \
-      return kLmError;                                                        \
-    }                                                                         \
-  } while (0)
-
-// `bytes` of device memory for `what`; a failure names the bytes asked for
-bool take(DevBuf &b, size_t bytes, const char *what) { return take(b, bytes, what, kWho); }
-
-// what the entry refuses before any HIP call
-int capture_single_faces_check(const CaptureSingleFacesArgs &sa) {
-  const CaptureFacesArgs &a = sa.cap;
-  if (!a.d_images || !a.d_pixel_map || !a.d_vertices || !a.d_faces || !a.d_normals || !a.leds || !a.view || !a.p0 || !sa.single_brdf) {
-    set_error("%s(): null images, pixel map, mesh, leds, view origin, p0 or single_brdf", kWho);
-    return kLmError;
-  }
-  if (a.L < 1 || a.L > 64 || a.H <= 0 || a.W <= 0 || a.nf <= 0 || a.nf > INT_MAX / 3) {
-    set_error("%s(): L = %d, H = %d, W = %d, nf = %d: need 1 <= L <= 64, H, W, nf > 0 and 3 nf <= INT_MAX", kWho, a.L, a.H, a.W, a.nf);
-    return kLmError;
-  }
-  MethodSpec ms;
-  if (!known_model_method(a.model, BRDF_METHOD_BC_DIF, &ms, kWho)) return kLmError;
-  if (a.v_min > a.v_max || a.cos_min != a.cos_min) {
-    set_error("%s(): bad validity rule (v_min %d > v_max %d, or cos_min not a number)", kWho, a.v_min, a.v_max);
-    return kLmError;
-  }
-  return box_refused(ms, a.lb, a.ub, kWho) ? kLmError : 0;
-}
-
 // levmar's n < m refusal of channel c: ret = LM_ERROR, zero info, p0
 void refuse_channel(const CaptureSingleFacesArgs &sa, int c) {
-  for (int k = 0; k < kM; ++k) sa.single_brdf[c * kM + k] = sa.cap.p0[k];
+  for (int k = 0; k < kM; ++k) sa.single_brdf[c * kM + k] = sa.g.cap.p0[k];
   if (sa.info)
     for (int k = 0; k < kInfoSz; ++k) sa.info[c * kInfoSz + k] = 0.0;
   if (sa.ret) sa.ret[c] = kLmError;
@@ -304,20 +191,19 @@ void refuse_channel(const CaptureSingleFacesArgs &sa, int c) {
 }  // namespace
 
 int capture_single_faces_run(const CaptureSingleFacesArgs &sa) {
-  if (capture_single_faces_check(sa) != 0) return kLmError;
-  const CaptureFacesArgs &a = sa.cap;
+  if (capture_args_check(kWho, sa.g, sa.single_brdf, "single_brdf") != 0) return kLmError;  // before any HIP call
+  const CaptureArgs &a = sa.g.cap;
   (void)hipGetLastError();
   hipStream_t stream = a.stream;
-  const int L = a.L, H = a.H, W = a.W;
-  if (a.n_pixels) *a.n_pixels = 0;
-  if (a.n_faces) *a.n_faces = 0;
+  if (sa.g.n_pixels) *sa.g.n_pixels = 0;
+  if (sa.g.n_faces) *sa.g.n_faces = 0;
   if (sa.count) sa.count[0] = sa.count[1] = sa.count[2] = 0;
   const bool want_stats = sa.covar || sa.stats || sa.rank;
   const bool want_faces = sa.d_face_sumsq || sa.d_face_count;
 
-  // ---- compact, group, cosines (capture_group.h) ----
+  // ---- compact, group, cosines (capture_group.hip) ----
   CaptureGroup g;
-  if (capture_group_run(kWho, a, g) != 0) return kLmError;
+  if (capture_group_run(kWho, sa.g, g) != 0) return kLmError;
   if (g.S == 0) {  // an empty capture: every channel is refused, nothing is written on the device but the pixel counts
     for (int c = 0; c < 3; ++c) refuse_channel(sa, c);
     if (sa.covar) std::fill(sa.covar, sa.covar + 3 * kM * kM, 0.0);  // (the ragged statistics of no sample)
@@ -325,42 +211,29 @@ int capture_single_faces_run(const CaptureSingleFacesArgs &sa) {
     if (sa.rank) sa.rank[0] = sa.rank[1] = sa.rank[2] = 0;
     return 3;
   }
-  const long long S = g.S, F = g.F, T = S * L;  // T: candidates of one channel
+  const long long F = g.F;
 
   // ---- count, scan ----
-  const int pb = (int)((T + kCT - 1) / kCT);
-  DevBuf pack_count, pack_off, seg;
-  if (!take(pack_count, sizeof(int) * 3 * (size_t)pb, "the candidate blocks' counts") ||
-      !take(pack_off, sizeof(long long) * 3 * (size_t)pb, "the candidate blocks' offsets") ||
-      !take(seg, sizeof(long long) * 3 * ((size_t)F + 1), "the faces' offsets"))
-    return kLmError;
   SinglePackCtx pc = {};
-  pc.images = a.d_images;
-  pc.L = L;
-  pc.H = H;
-  pc.W = W;
-  pc.pixel_sorted = g.pixel_sorted.as<long long>();
-  pc.face_sorted = g.face_sorted.as<unsigned>();
-  pc.rank_of_face = g.rank_of_face.as<int>();
-  pc.face_first = g.face_first.as<long long>();
-  pc.angles_f = g.angles_f.as<double>();
-  pc.T = T;
-  pc.F = (int)F;
-  pc.v_min = a.v_min;
-  pc.v_max = a.v_max;
-  pc.cos_min = a.cos_min;
-  pc.use1 = a.model != MODEL_PHONG;
-  pc.use2 = a.model != MODEL_BLINN_PHONG;
+  pc.cand = capture_candidates(sa.g, g);
+  const long long T = pc.cand.T;  // candidates of one channel
+  const int pb = (int)((T + kCT - 1) / kCT);
+  DevBuf pack_count, pack_off, seg, totals;
+  if (!take(pack_count, sizeof(int) * 3 * (size_t)pb, "the candidate blocks' counts", kWho) ||
+      !take(pack_off, sizeof(long long) * 3 * (size_t)pb, "the candidate blocks' offsets", kWho) ||
+      !take(seg, sizeof(long long) * 3 * ((size_t)F + 1), "the faces' offsets", kWho) || !take(totals, sizeof(long long) * 3, "the channels' totals", kWho))
+    return kLmError;
   pc.block_count = pack_count.as<int>();
   pc.block_off = pack_off.as<long long>();
   pc.seg = seg.as<long long>();
   hipLaunchKernelGGL(single_pack_faces_kernel<0>, dim3(pb), dim3(kCT), 0, stream, pc);
-  hipLaunchKernelGGL(single_scan_kernel, dim3(1), dim3(kCT), 0, stream, pack_count.as<int>(), (long long)pb, pack_off.as<long long>(), seg.as<long long>(),
-                     (int)F, g.head.as<long long>());
-  SINGLE_OK(hipGetLastError());
+  // every channel from 0: its end is K_c, also the end of the channel's face offsets, seg[c][F]
+  hipLaunchKernelGGL(block_scan3_kernel<false>, dim3(1), dim3(kCT), 0, stream, pack_count.as<int>(), (long long)pb, pack_off.as<long long>(),
+                     seg.as<long long>() + F, F + 1, totals.as<long long>());
+  CAPTURE_OK(kWho, hipGetLastError());
   long long K[3] = {0, 0, 0};
-  SINGLE_OK(hipMemcpyAsync(K, g.head.ptr, sizeof K, hipMemcpyDeviceToHost, stream));
-  SINGLE_OK(hipStreamSynchronize(stream));
+  CAPTURE_OK(kWho, hipMemcpyAsync(K, totals.ptr, sizeof K, hipMemcpyDeviceToHost, stream));
+  CAPTURE_OK(kWho, hipStreamSynchronize(stream));
   for (int c = 0; c < 3; ++c) {
     if (K[c] < 0 || K[c] > T) {
       set_error("%s(): the count finds %lld valid samples among %lld candidates of channel %d", kWho, K[c], T, c);
@@ -380,14 +253,14 @@ int capture_single_faces_run(const CaptureSingleFacesArgs &sa) {
     doubles += (4 * (size_t)K[c] + kAlign - 1) / kAlign * kAlign;
   }
   DevBuf packed;
-  if (!take(packed, sizeof(double) * doubles, "the channels' planes and measurements")) return kLmError;
+  if (!take(packed, sizeof(double) * doubles, "the channels' planes and measurements", kWho)) return kLmError;
   for (int c = 0; c < 3; ++c) {
     pc.ang[c] = packed.as<double>() + start[c];
     pc.x[c] = pc.ang[c] + 3 * (size_t)K[c];
     pc.K[c] = K[c];
   }
   hipLaunchKernelGGL(single_pack_faces_kernel<1>, dim3(pb), dim3(kCT), 0, stream, pc);
-  SINGLE_OK(hipGetLastError());
+  CAPTURE_OK(kWho, hipGetLastError());
 
   // ---- fit: "do the calculation once for each color-channel", brdfdata.cpp:1161, one dlevmar_bc_dif (:1058) each ----
   int failed = 0;
@@ -420,20 +293,20 @@ int capture_single_faces_run(const CaptureSingleFacesArgs &sa) {
   DevBuf small;  // p [3][3], covar [3][9], stats [3][kStatsSz], three staged rows of 12 doubles; rank [3], counts [3]
   constexpr int kSmallD = 3 * kM + 3 * kM * kM + 3 * kStatsSz + 3 * 12;
   if (want_stats) {
-    if (!take(small, sizeof(double) * kSmallD + sizeof(int) * 6, "the channels' statistics")) return kLmError;
+    if (!take(small, sizeof(double) * kSmallD + sizeof(int) * 6, "the channels' statistics", kWho)) return kLmError;
     double *d_p = small.as<double>(), *d_covar = d_p + 3 * kM, *d_stats = d_covar + 3 * kM * kM, *d_stage = d_stats + 3 * kStatsSz;
     int *d_rank = reinterpret_cast<int *>(d_stage + 3 * 12), *d_cnt = d_rank + 3;
-    SINGLE_OK(hipMemsetAsync(small.ptr, 0, sizeof(double) * kSmallD + sizeof(int) * 6, stream));
-    SINGLE_OK(hipMemcpyAsync(d_p, p3, sizeof p3, hipMemcpyHostToDevice, stream));
-    SINGLE_OK(hipMemcpyAsync(d_cnt, h_cnt, sizeof h_cnt, hipMemcpyHostToDevice, stream));
+    CAPTURE_OK(kWho, hipMemsetAsync(small.ptr, 0, sizeof(double) * kSmallD + sizeof(int) * 6, stream));
+    CAPTURE_OK(kWho, hipMemcpyAsync(d_p, p3, sizeof p3, hipMemcpyHostToDevice, stream));
+    CAPTURE_OK(kWho, hipMemcpyAsync(d_cnt, h_cnt, sizeof h_cnt, hipMemcpyHostToDevice, stream));
     for (int c = 0; c < 3; ++c) {
       FitStatsArgs f = {BRDF_METHOD_BC_DIF, a.model, pc.ang[c], pc.x[c], 1, (int)K[c], d_p + c * kM, a.opts, d_covar + c * kM * kM, d_stats + c * kStatsSz,
                         d_rank + c, nullptr, 0, stream, nullptr};
       if (K[c] < kM) {
         double *row = d_stage + c * 12;  // planes [3][3], x [3]: the channel's K_c samples at the front of each
         for (int k = 0; k < 3 && K[c] > 0; ++k)
-          SINGLE_OK(hipMemcpyAsync(row + 3 * k, pc.ang[c] + k * K[c], sizeof(double) * K[c], hipMemcpyDeviceToDevice, stream));
-        if (K[c] > 0) SINGLE_OK(hipMemcpyAsync(row + 9, pc.x[c], sizeof(double) * K[c], hipMemcpyDeviceToDevice, stream));
+          CAPTURE_OK(kWho, hipMemcpyAsync(row + 3 * k, pc.ang[c] + k * K[c], sizeof(double) * K[c], hipMemcpyDeviceToDevice, stream));
+        if (K[c] > 0) CAPTURE_OK(kWho, hipMemcpyAsync(row + 9, pc.x[c], sizeof(double) * K[c], hipMemcpyDeviceToDevice, stream));
         f.d_angles = row;
         f.d_x = row + 9;
         f.n = kM;
@@ -441,9 +314,9 @@ int capture_single_faces_run(const CaptureSingleFacesArgs &sa) {
       }
       if (fit_stats_enqueue(f, kWho) != 0) return kLmError;
     }
-    if (sa.covar) SINGLE_OK(hipMemcpyAsync(sa.covar, d_covar, sizeof(double) * 3 * kM * kM, hipMemcpyDeviceToHost, stream));
-    if (sa.stats) SINGLE_OK(hipMemcpyAsync(sa.stats, d_stats, sizeof(double) * 3 * kStatsSz, hipMemcpyDeviceToHost, stream));
-    if (sa.rank) SINGLE_OK(hipMemcpyAsync(sa.rank, d_rank, sizeof(int) * 3, hipMemcpyDeviceToHost, stream));
+    if (sa.covar) CAPTURE_OK(kWho, hipMemcpyAsync(sa.covar, d_covar, sizeof(double) * 3 * kM * kM, hipMemcpyDeviceToHost, stream));
+    if (sa.stats) CAPTURE_OK(kWho, hipMemcpyAsync(sa.stats, d_stats, sizeof(double) * 3 * kStatsSz, hipMemcpyDeviceToHost, stream));
+    if (sa.rank) CAPTURE_OK(kWho, hipMemcpyAsync(sa.rank, d_rank, sizeof(int) * 3, hipMemcpyDeviceToHost, stream));
   }
 
   // ---- residuals of every carried face against its channel's fit ----
@@ -460,8 +333,8 @@ int capture_single_faces_run(const CaptureSingleFacesArgs &sa) {
         return kLmError;
       }
     }
-    if (!take(chunk_first, sizeof(long long) * 3 * ((size_t)F + 1), "the faces' first chunks") ||
-        !take(partial, sizeof(double) * pdoubles, "the chunks' partial sums"))
+    if (!take(chunk_first, sizeof(long long) * 3 * ((size_t)F + 1), "the faces' first chunks", kWho) ||
+        !take(partial, sizeof(double) * pdoubles, "the chunks' partial sums", kWho))
       return kLmError;
     hipLaunchKernelGGL(resid_scan_kernel, dim3(3), dim3(kCT), 0, stream, seg.as<long long>(), (int)F, chunk_first.as<long long>());
     ResidFoldCtx fc = {};
@@ -487,9 +360,9 @@ int capture_single_faces_run(const CaptureSingleFacesArgs &sa) {
       hipLaunchKernelGGL(resid_kernel_of(a.model), dim3(grid), dim3(kCT), 0, stream, rc);
     }
     hipLaunchKernelGGL(resid_fold_kernel, dim3((unsigned)((F + kCT - 1) / kCT)), dim3(kCT), 0, stream, fc);
-    SINGLE_OK(hipGetLastError());
+    CAPTURE_OK(kWho, hipGetLastError());
   }
-  SINGLE_OK(hipStreamSynchronize(stream));
+  CAPTURE_OK(kWho, hipStreamSynchronize(stream));
   return failed;
 }
 

@@ -17,6 +17,7 @@
 // (L = 16: 384 B), i.e. 496 B of algorithmic traffic per surfel.
 #include <cstdio>
 
+#include "capture_fit.h"
 #include "fit_host.h"
 
 namespace brdf {

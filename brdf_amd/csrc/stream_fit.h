@@ -100,76 +100,6 @@ int channels_fit_run(int method, int model, const double *d_angles, const double
 int channels_last_shared();           // 1: the last channels_fit_run on this thread was one shared launch
 FitStats channels_last_stats(int c);  // channel c of that call
 
-int capture_fit_single_run(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
-                           const double *d_vertices, const int *d_faces, const double *d_normals, int nf, const double *leds,
-                           const double *view, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
-                           const double *opts, double *single_brdf, double *info, long long *n_faces_used, hipStream_t stream);
-// vectors -> cosines (cosines.hip)
-int cosines_run(const double *d_vertices, const int *d_faces, const double *d_normals, const int *d_surfels, long long S,
-                const double *leds, int L, const double *view, int rv_mode, double *d_angles, hipStream_t stream);
-void led_table(double *out16x3);
-// the pixel loop of CalcBRDFEquation (capture_fit.hip)
-// the validity rule of brdf_hip_fit_capture_masked_dev: sample i of a fit takes part iff v_min <= 8-bit intensity <= v_max and every
-// cosine plane the model reads is > cos_min; d_surface_count[nf][3] (device, or null) receives the stored fits' sample counts
-struct CaptureMask {
-  int v_min, v_max;
-  double cos_min;
-  int *d_surface_count;
-};
-int capture_fit_run(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
-                    const double *d_vertices, const int *d_faces, const double *d_normals, int nf, const double *leds,
-                    const double *view, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
-                    const double *opts, double *d_brdf_surfaces, double *avg, long long *n_pixels, hipStream_t stream,
-                    double *d_surface_covar = nullptr, double *d_surface_stats = nullptr, int *d_surface_rank = nullptr,  // the optional statistics tail
-                    const CaptureMask *mask = nullptr);  // brdf_hip_fit_capture_masked_dev: a validity rule, a ragged fit
-
-// brdf_hip_fit_capture_faces_dev (capture_faces.hip): one fit per (face, channel) over the valid samples of all the face's pixels,
-// through the packed batch.  The capture, the mesh and the fit's settings as capture_fit_run; the rule as CaptureMask.
-struct CaptureFacesArgs {
-  int model;
-  const unsigned char *d_images;
-  int L, H, W;
-  const int *d_pixel_map;
-  const double *d_vertices;
-  const int *d_faces;
-  const double *d_normals;
-  int nf;
-  const double *leds, *view;
-  int rv_mode;
-  const double *p0, *lb, *ub;
-  int itmax;
-  const double *opts;
-  int v_min, v_max;
-  double cos_min;
-  long long workspace_bytes;  // the packed calls'
-  double *d_brdf_surfaces;    // [nf][3][3]
-  double *d_surface_info;     // [nf][3][10] or null
-  int *d_surface_ret;         // [nf][3] or null
-  double *d_surface_covar, *d_surface_stats;  // [nf][3][9], [nf][3][kStatsSz] or null
-  int *d_surface_rank, *d_surface_count;      // [nf][3] or null
-  int *d_face_pixels;                         // [nf] or null
-  double *avg;                                // host [3] or null
-  long long *n_pixels, *n_faces;              // host or null
-  hipStream_t stream;
-};
-int capture_faces_run(const CaptureFacesArgs &a);  // refuses bad arguments before any HIP call
-
-// brdf_hip_fit_capture_single_faces_dev (capture_single_faces.hip): ONE fit per channel over the valid samples of every pixel of every
-// carried face, through the single-fit path, and the carried faces' sums of squared residuals against that fit.
-struct CaptureSingleFacesArgs {
-  CaptureFacesArgs cap;  // the capture, the mesh, the fit's settings, the rule, d_face_pixels, n_pixels, n_faces, stream; its
-                         // workspace_bytes, [nf][3] maps and avg are not read
-  double *single_brdf;   // host [3][3], required
-  double *info;          // host [3][10] or null
-  int *ret;              // host [3] or null
-  double *covar, *stats;  // host [3][9], [3][kStatsSz] or null
-  int *rank;              // host [3] or null
-  long long *count;       // host [3] or null: the samples of channel c's fit
-  double *d_face_sumsq;   // [nf][3] or null
-  int *d_face_count;      // [nf][3] or null
-};
-int capture_single_faces_run(const CaptureSingleFacesArgs &a);  // refuses bad arguments before any HIP call; the channels with ret < 0
-
 // one model evaluation / analytic Jacobian over n samples (stream_fit.hip): d_hx [n], d_jac [n][3]
 int model_eval_run(int model, const double *d_angles, int n, const double *p, double *d_hx, hipStream_t stream);
 int model_jac_run(int model, const double *d_angles, int n, const double *p, double *d_jac, hipStream_t stream);

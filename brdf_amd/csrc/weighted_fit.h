@@ -35,11 +35,4 @@ struct WeightedStatsArgs {
 int weighted_stats_check(const WeightedStatsArgs &a, const char *who);
 int weighted_stats_enqueue(const WeightedStatsArgs &a, const char *who);
 
-// brdf_hip_fit_capture_means_dev (capture_means.hip): the per-face capture as a weighted fit of per-light means
-struct CaptureMeansArgs {
-  CaptureFacesArgs faces;  // brdf_hip_fit_capture_faces_dev's arguments (workspace_bytes unused; d_surface_count receives k)
-  int *d_surface_lights;   // [nf][3] or null: the lights with a sample, the weighted fit's n
-};
-int capture_means_run(const CaptureMeansArgs &a);
-
 }  // namespace brdf

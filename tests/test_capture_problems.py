@@ -52,7 +52,7 @@ def test_big_capture_reaches_the_multi_item_scans():
     assert int((pm == nf).sum()) == 40 and int((pm == -5).sum()) == 40
     assert int((pm == cap["big_face"]).sum()) == 300
     candidates = g.size * 16
-    assert (candidates + P.KCT - 1) // P.KCT == 282 > 256  # pack blocks: pack_scan_kernel's threads own two each
+    assert (candidates + P.KCT - 1) // P.KCT == 282 > 256  # pack blocks: block_scan3_kernel's threads own two each
     assert (3 * carried.size + P.KCT - 1) // P.KCT == 8  # scatter blocks
     assert (nf + P.KCT - 1) // P.KCT > 1  # face_scan_kernel: 274 faces per thread
     counts = np.diff(_big_group(1)[2])
