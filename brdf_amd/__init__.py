@@ -11,4 +11,5 @@ from .fit import (METHOD_BC_DER, METHOD_BC_DIF, METHOD_DER, METHOD_DIF, MODEL_BL
                   fit_batch_packed, fit_stats_batch_packed, last_packed_stats, pack_samples, last_batch_launch,
                   CaptureFaces, fit_capture_faces, group_capture_samples,
                   fit_batch_weighted, fit_stats_batch_weighted, CaptureMeans, LightMeans, fit_capture_means, capture_light_means,
-                  CaptureSingleFaces, SingleSamples, fit_capture_single_faces, group_capture_single_samples)
+                  CaptureSingleFaces, SingleSamples, fit_capture_single_faces, group_capture_single_samples,
+                  ClippedFit, CaptureFacesClipped, SIGMA_MIN_8BIT, fit_batch_packed_clipped, fit_capture_faces_clipped, clip_samples, last_clip_stats)

@@ -79,6 +79,12 @@ ABI = {
     "brdf_hip_fit_stats_batch_packed_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, D, C.c_void_p,
                                                       C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "brdf_hip_fit_stats_batch_packed": (C.c_int, [C.c_int, C.c_int, D, D, C.POINTER(C.c_longlong), C.c_int, D, D, D, D, I, C.c_longlong]),
+    "brdf_hip_fit_batch_packed_clipped_dev": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, D, D, C.c_int, D,
+                                                        C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "brdf_hip_fit_batch_packed_clipped": (C.c_int, [C.c_int, C.c_int, D, D, C.POINTER(C.c_longlong), C.c_int, D, D, D, C.c_int, D, C.c_double,
+                                                    C.c_double, C.c_int, D, I, D, D, I, I, I, C.POINTER(C.c_ubyte), C.c_longlong]),
+    "brdf_hip_last_clip_stats": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "brdf_hip_last_packed_stats": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), I, I]),
     "brdf_hip_last_batch_launch": (C.c_int, [I, I, C.POINTER(C.c_longlong), I, I]),
     "brdf_hip_model_eval_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, D, C.c_void_p, C.c_void_p]),
@@ -101,6 +107,11 @@ ABI = {
                                                  C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, C.c_int, C.c_int, C.c_double,
                                                  C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, D, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p]),
+    "brdf_hip_fit_capture_faces_clipped_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, C.c_int, C.c_int, C.c_double,
+                                                         C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, D, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p,
+                                                         C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p]),
     "brdf_hip_fit_capture_means_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, C.c_int, C.c_int, C.c_double,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -19,6 +19,7 @@
 #include "capture_fit.h"
 #include "fit_host.h"
 #include "fit_stats.h"
+#include "clip_fit.h"
 #include "packed_fit.h"
 #include "weighted_fit.h"
 
@@ -697,6 +698,49 @@ int brdf_hip_fit_stats_batch_packed(int method, int model, const double *angles,
   return 0;
 }
 
+/* ---- sigma-clipped packed batches (clip_fit.hip) ------------------------------------------------------------------------------- */
+int brdf_hip_fit_batch_packed_clipped_dev(int method, int model, const double *d_angles, const double *d_x, const long long *d_offsets, int S,
+                                          double *d_p, const double *lb, const double *ub, int itmax, const double *opts, double kappa,
+                                          double sigma_min, int rounds, double *d_info, int *d_ret, double *d_covar, double *d_stats, int *d_rank,
+                                          int *d_kept, int *d_rounds_used, unsigned char *d_mask, long long workspace_bytes, void *stream) {
+  const ClipFitArgs a = {{method, model, d_angles, d_x, d_offsets, S, d_p, lb, ub, itmax, opts, d_info, d_ret, workspace_bytes, static_cast<hipStream_t>(stream)},
+                         {kappa, sigma_min, rounds}, d_covar, d_stats, d_rank, d_kept, d_rounds_used, d_mask};
+  return clip_fit_run(a, "brdf_hip_fit_batch_packed_clipped_dev");
+}
+
+int brdf_hip_fit_batch_packed_clipped(int method, int model, const double *angles, const double *x, const long long *offsets, int S, double *p,
+                                      const double *lb, const double *ub, int itmax, const double *opts, double kappa, double sigma_min, int rounds,
+                                      double *info, int *ret, double *covar, double *stats, int *rank, int *kept, int *rounds_used,
+                                      unsigned char *mask, long long workspace_bytes) {
+  const char *who = "brdf_hip_fit_batch_packed_clipped";
+  ClipFitArgs a = {{method, model, angles, x, offsets, S, p, lb, ub, itmax, opts, info, ret, workspace_bytes, nullptr},  // (host pointers: checked for null only)
+                   {kappa, sigma_min, rounds}, covar, stats, rank, kept, rounds_used, mask};
+  if (clip_fit_check(a, who) != 0 || check_host_offsets(who, offsets, S) != 0) return LM_ERROR;
+  std::vector<int> own_ret(ret ? 0 : S);
+  if (!ret) ret = own_ret.data();
+  HostCall h(who);
+  upload_packed(h, angles, x, offsets, S, &a.fit.d_angles, &a.fit.d_x, &a.fit.d_offsets);
+  a.fit.d_p = h.inout(p, 3 * (size_t)S);
+  a.fit.d_info = h.out(info, 10 * (size_t)S);
+  a.fit.d_ret = h.out(ret, S);
+  a.d_covar = h.out(covar, 9 * (size_t)S);
+  a.d_stats = h.out(stats, BRDF_STATS_SZ * (size_t)S);
+  a.d_rank = h.out(rank, S);
+  a.d_kept = h.out(kept, S);
+  a.d_rounds_used = h.out(rounds_used, S);
+  a.d_mask = h.out(mask, (size_t)(offsets[S] - offsets[0]));
+  if (h.failed() || clip_fit_run(a, who) != 0 || h.finish() != 0) return LM_ERROR;
+  return count_failed(ret, S);
+}
+
+int brdf_hip_last_clip_stats(int round, long long *active_fits, long long *clipped_samples) {
+  const ClipLastStats st = clip_last_stats();
+  if (round < 1 || round > st.rounds) return LM_ERROR;
+  if (active_fits) *active_fits = st.active[round - 1];
+  if (clipped_samples) *clipped_samples = st.clipped[round - 1];
+  return 0;
+}
+
 int brdf_hip_last_packed_stats(int cls, long long *fits, int *stride, int *chunks) {
   if (cls < 0 || cls >= kPackedClasses) return LM_ERROR;
   const PackedLastStats st = packed_last_stats();
@@ -779,6 +823,20 @@ int brdf_hip_fit_capture_faces_dev(int model, const unsigned char *d_images, int
                                    long long *n_pixels, long long *n_faces, void *stream) {
   const CaptureFacesArgs a = {{CAPTURE_ARGS, v_min, v_max, cos_min, d_face_pixels, n_pixels, n_faces}, workspace_bytes, d_brdf_surfaces, d_surface_info,
                               d_surface_ret, d_surface_covar, d_surface_stats, d_surface_rank, d_surface_count, avg};
+  return capture_faces_run(a);
+}
+
+int brdf_hip_fit_capture_faces_clipped_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                           const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                           const double *view_origin, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
+                                           const double *opts, int v_min, int v_max, double cos_min, long long workspace_bytes,
+                                           double *d_brdf_surfaces, double *d_surface_info, int *d_surface_ret, double *d_surface_covar,
+                                           double *d_surface_stats, int *d_surface_rank, int *d_surface_count, int *d_face_pixels, double *avg,
+                                           long long *n_pixels, long long *n_faces, void *stream, double kappa, double sigma_min, int rounds,
+                                           int *d_surface_kept, int *d_surface_rounds) {
+  const CaptureClip clip = {kappa, sigma_min, rounds, d_surface_kept, d_surface_rounds};
+  const CaptureFacesArgs a = {{CAPTURE_ARGS, v_min, v_max, cos_min, d_face_pixels, n_pixels, n_faces}, workspace_bytes, d_brdf_surfaces, d_surface_info,
+                              d_surface_ret, d_surface_covar, d_surface_stats, d_surface_rank, d_surface_count, avg, &clip};
   return capture_faces_run(a);
 }
 

@@ -68,6 +68,13 @@ struct CaptureGrouped {
   long long *n_pixels, *n_faces;  // host or null
 };
 
+// brdf_hip_fit_capture_faces_clipped_dev: the sigma clip of the per-face fits (clip_fit.h) and its two maps
+struct CaptureClip {
+  double kappa, sigma_min;
+  int rounds;
+  int *d_surface_kept, *d_surface_rounds;  // [nf][3] or null: the returned set's size, rounds_used
+};
+
 // brdf_hip_fit_capture_faces_dev (capture_faces.hip): one fit per (face, channel) over the valid samples of all the face's pixels,
 // through the packed batch
 struct CaptureFacesArgs {
@@ -79,6 +86,7 @@ struct CaptureFacesArgs {
   double *d_surface_covar, *d_surface_stats;  // [nf][3][9], [nf][3][kStatsSz] or null
   int *d_surface_rank, *d_surface_count;      // [nf][3] or null
   double *avg;                                // host [3] or null
+  const CaptureClip *clip = nullptr;          // null: brdf_hip_fit_capture_faces_dev; otherwise the clipped entry, under its own name
 };
 int capture_faces_run(const CaptureFacesArgs &a);  // refuses bad arguments before any HIP call
 

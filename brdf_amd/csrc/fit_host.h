@@ -174,7 +174,7 @@ class HostCall {
   const char *who_;
   bool failed_ = false;
   std::vector<Download> downloads_;
-  std::tuple<std::deque<DeviceBlock<double>>, std::deque<DeviceBlock<int>>, std::deque<DeviceBlock<long long>>> blocks_;
+  std::tuple<std::deque<DeviceBlock<double>>, std::deque<DeviceBlock<int>>, std::deque<DeviceBlock<long long>>, std::deque<DeviceBlock<unsigned char>>> blocks_;
 };
 
 // ---- what the batched entries refuse ------------------------------------------------------------------------------------------

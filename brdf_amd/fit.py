@@ -406,6 +406,89 @@ def fit_stats_batch_packed(method: int, model: int, angles, x, offsets, p, *, op
     return st
 
 
+class ClippedFit(NamedTuple):
+    """What fit_batch_packed_clipped returns (CUDA tensors)."""
+    p: object            # [S,3] float64
+    info: object         # [S,10] float64
+    ret: object          # [S] int32
+    stats: FitStats      # covar [S,3,3], stats [S,8], rank [S]: at p over the returned sample set
+    kept: object         # [S] int32: the samples of the fit's returned set
+    rounds_used: object  # [S] int32: the last clip round that refitted the fit (0: none)
+    mask: object         # [offsets[S] - offsets[0]] uint8: 1 = in the returned set, by the caller's sample position
+
+
+SIGMA_MIN_8BIT = 1.0 / (255.0 * 12.0 ** 0.5)  # the standard deviation of an 8-bit capture's quantisation: the recommended sigma_min
+
+
+def fit_batch_packed_clipped(method: int, model: int, angles, x, offsets, p0, *, kappa: float, sigma_min: float, rounds: int, lb=None, ub=None,
+                             itmax=100, opts=None, workspace_bytes: int = 0, validate: bool = True) -> ClippedFit:
+    """fit_batch_packed with sigma clipping (brdf_hip_fit_batch_packed_clipped_dev): fit, drop the samples further than kappa * sigma
+    from the fit, fit the survivors again from the current p, at most `rounds` times or until nothing more is dropped.  Arguments as
+    fit_batch_packed.  sigma = max(sqrt(sumsq / (k - 3)), sigma_min) with the statistics pass's sumsq over the fit's current k samples
+    (k == 3: sigma_min; SIGMA_MIN_8BIT is recommended for 8-bit captures); a fit that is refused, ends with ret < 0, drops nothing or
+    would keep fewer than 3 samples is settled and keeps its samples.  Every returned fit is a fit of its returned sample set: p,
+    info and ret have fit_batch_packed's bytes on that set from the previous round's p, `stats` fit_stats_batch_packed's at p.
+    rounds = 0 or kappa = inf return the two packed calls' bytes.  With rounds > 0 the offsets must not descend (refused on the device, also
+    with validate=False).  clip_samples is one clip round of this definition as NumPy code."""
+    import torch
+    angles, x, offsets, p = _packed_args(angles, x, offsets, p0, validate, torch)
+    S = offsets.numel() - 1
+    dev = x.device
+    total = int(offsets[-1]) - int(offsets[0])
+    _require(total >= 0, "offsets[S] < offsets[0]")
+    info = torch.zeros((S, 10), dtype=torch.float64, device=dev)
+    ret, kept, used = (torch.zeros((S,), dtype=torch.int32, device=dev) for _ in range(3))
+    mask = torch.zeros((total,), dtype=torch.uint8, device=dev)
+    st = _zero_stats((S,), dev)
+    lb_a, ub_a, op_a = _f64(lb, 3), _f64(ub, 3), _f64(opts, 5)
+    _call("brdf_hip_fit_batch_packed_clipped_dev", dev, method, model, angles.data_ptr(), x.data_ptr(), offsets.data_ptr(), S, p.data_ptr(), _dptr(lb_a),
+          _dptr(ub_a), itmax, _dptr(op_a), float(kappa), float(sigma_min), int(rounds), info.data_ptr(), ret.data_ptr(), st.covar.data_ptr(),
+          st.stats.data_ptr(), st.rank.data_ptr(), kept.data_ptr(), used.data_ptr(), mask.data_ptr(), int(workspace_bytes), _STREAM)
+    return ClippedFit(p, info, ret, st, kept, used, mask)
+
+
+def last_clip_stats() -> list:
+    """per clip round of this thread's last clipped call: the fits that were clipped and refitted, and the samples dropped"""
+    out = []
+    active, clipped = C.c_longlong(0), C.c_longlong(0)
+    while lib.brdf_hip_last_clip_stats(len(out) + 1, C.byref(active), C.byref(clipped)) == 0:
+        out.append({"active": active.value, "clipped": clipped.value})
+    return out
+
+
+def clip_samples(model: int, angles, x, offsets, p, sumsq, ret, *, kappa: float, sigma_min: float):
+    """ONE clip round of fit_batch_packed_clipped's definition, as NumPy code on the host (no device): the packed batch angles
+    [3 * total], x [total], offsets [S+1] holds the fits' CURRENT sample sets, p [S,3] their current parameters, sumsq [S] the
+    statistics pass's stats[:, 0] at p over those sets, ret [S] the fits' ret.  Returns (keep [offsets[S] - offsets[0]] bool, by sample
+    position, and settled [S] bool).  For a fit with ret < 0, fewer than 3 samples or a sumsq that is not finite: settled, all kept.
+    Otherwise sigma = max(sqrt(sumsq / (k - 3)), sigma_min) (k == 3: sigma_min) and sample i survives iff |x_i - f_i(p)| <= kappa *
+    sigma (a NaN residual does not); nothing dropped, or fewer than 3 survivors: settled, all kept.  The caller marks settled fits and
+    never passes them as unsettled again: here every fit given is looked at."""
+    from . import synth
+    angles, x = np.asarray(angles, dtype=np.float64), np.asarray(x, dtype=np.float64)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    p, sumsq, ret = np.asarray(p, dtype=np.float64), np.asarray(sumsq, dtype=np.float64), np.asarray(ret)
+    S = offsets.size - 1
+    _require(p.shape == (S, 3) and sumsq.shape == (S,) and ret.shape == (S,), "p [S,3], sumsq [S], ret [S]")
+    o0 = int(offsets[0])
+    keep = np.ones(int(offsets[-1]) - o0, dtype=bool)
+    settled = np.ones(S, dtype=bool)
+    for s in range(S):
+        o, k = int(offsets[s]), int(offsets[s + 1] - offsets[s])
+        if ret[s] < 0 or k < 3 or not np.isfinite(sumsq[s]):
+            continue
+        a = angles[3 * o:3 * o + 3 * k].reshape(3, k)
+        with np.errstate(all="ignore"):
+            sigma = max(float(np.sqrt(sumsq[s] / (k - 3))), float(sigma_min)) if k > 3 else float(sigma_min)
+            e = x[o:o + k] - synth.model_value(model, p[s], a[0], a[1], a[2])
+            ok = np.abs(e) <= np.float64(kappa) * np.float64(sigma)  # (False for a NaN)
+        if ok.all() or int(ok.sum()) < 3:
+            continue
+        keep[o - o0:o - o0 + k] = ok
+        settled[s] = False
+    return keep, settled
+
+
 def last_packed_stats() -> list:
     """per size class 0..5 (<= 16, 64, 256, 1024, 4096 samples, above) of this thread's last packed call: fits, the row stride of its
     launches (0: empty class; class 5: the largest count) and chunks (class 5: one run per fit)"""
@@ -654,6 +737,59 @@ def fit_capture_faces(model: int, images, pixel_map, vertices, faces, face_norma
           None if st is None else st.rank.data_ptr(), out.count.data_ptr(), out.face_pixels.data_ptr(), _dptr(avg), C.byref(npx), C.byref(nfc),
           _STREAM)
     return CaptureFaces(out.surfaces, out.info, out.ret, st, out.count, out.face_pixels, avg, npx.value, nfc.value)
+
+
+class CaptureFacesClipped(NamedTuple):
+    """What fit_capture_faces_clipped returns: CaptureFaces' fields and the clip's two maps."""
+    surfaces: object
+    info: object
+    ret: object
+    stats: FitStats | None
+    count: object        # [nf,3] int32: the fit's candidate samples under the validity rule
+    face_pixels: object
+    avg: np.ndarray
+    n_pixels: int
+    n_faces: int
+    kept: object         # [nf,3] int32: the samples of the fit's returned set
+    rounds: object       # [nf,3] int32: rounds_used
+
+
+def fit_capture_faces_clipped(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, kappa: float, sigma_min: float,
+                              rounds: int, v_min: int = 0, v_max: int = 255, cos_min: float = -2.0, rv_mode: int = 0, p0=(0.5, 1.0, 1.0),
+                              lb=(0.0, 0.0, 0.0), ub=(100.0, 100.0, 100.0), itmax: int = 100, opts=None, workspace_bytes: int = 0,
+                              want_stats: bool = True, validate: bool = True, out: CaptureFacesClipped | None = None) -> CaptureFacesClipped:
+    """fit_capture_faces with fit_batch_packed_clipped in place of the packed fit and statistics
+    (brdf_hip_fit_capture_faces_clipped_dev): everything in front of the fit and the scatter behind it are fit_capture_faces'.  `count`
+    keeps its meaning, `kept` is the returned sample set's size and `rounds` rounds_used; faces no pixel carries keep zeros in both.
+    The statistics are taken over the returned sets.  rounds = 0 gives fit_capture_faces' bytes in every map and scalar.  `out`: an
+    earlier result (or one built by hand) whose tensors are written into, as in fit_capture_faces."""
+    import torch
+    args, keep, nf = _capture_args(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, rv_mode, p0, lb, ub, itmax, opts,
+                                   validate)
+    dev = keep[0].device
+
+    def z(*shape, dtype=torch.float64):
+        return torch.zeros((nf, *shape), dtype=dtype, device=dev)
+    if out is None:
+        out = CaptureFacesClipped(z(3, 3), z(3, 10), z(3, dtype=torch.int32), _zero_stats((nf, 3), dev) if want_stats else None, z(3, dtype=torch.int32),
+                                  z(dtype=torch.int32), None, 0, 0, z(3, dtype=torch.int32), z(3, dtype=torch.int32))
+    _require(not want_stats or out.stats is not None, "out: want_stats needs out.stats")
+    surfaces, info, ret, count, face_pixels, kept, used = out.surfaces, out.info, out.ret, out.count, out.face_pixels, out.kept, out.rounds
+    st = out.stats if want_stats else None
+    maps = [(surfaces, (nf, 3, 3), torch.float64), (info, (nf, 3, 10), torch.float64), (face_pixels, (nf,), torch.int32)]
+    maps += [(t, (nf, 3), torch.int32) for t in (ret, count, kept, used)]
+    if st is not None:
+        maps += [(st.covar, (nf, 3, 3, 3), torch.float64), (st.stats, (nf, 3, 8), torch.float64), (st.rank, (nf, 3), torch.int32)]
+    for t, shape, dtype in maps:
+        _require(t.is_cuda and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(),
+                 f"out: contiguous CUDA {dtype} {list(shape)} tensors on the capture's device")
+    avg = np.zeros(3)
+    npx, nfc = C.c_longlong(0), C.c_longlong(0)
+    _call("brdf_hip_fit_capture_faces_clipped_dev", dev, *args, int(v_min), int(v_max), float(cos_min), int(workspace_bytes), surfaces.data_ptr(),
+          info.data_ptr(), ret.data_ptr(), None if st is None else st.covar.data_ptr(), None if st is None else st.stats.data_ptr(),
+          None if st is None else st.rank.data_ptr(), count.data_ptr(), face_pixels.data_ptr(), _dptr(avg), C.byref(npx), C.byref(nfc), _STREAM,
+          float(kappa), float(sigma_min), int(rounds), kept.data_ptr(), used.data_ptr())
+    return CaptureFacesClipped(surfaces, info, ret, st, count, face_pixels, avg, npx.value, nfc.value, kept, used)
 
 
 def group_capture_samples(images, pixel_map, face_angles, model: int, *, v_min: int = 0, v_max: int = 255, cos_min: float = -2.0):

@@ -366,6 +366,64 @@ int brdf_hip_fit_stats_batch_packed_dev(int method, int model, const double *d_a
                                         long long workspace_bytes, void *stream);
 int brdf_hip_fit_stats_batch_packed(int method, int model, const double *angles, const double *x, const long long *offsets, int S,
                                     const double *p, const double *opts, double *covar, double *stats, int *rank, long long workspace_bytes);
+/* ---- sigma-clipped packed batches (extensions) ------------------------------------------------------------------------------ */
+/* Fit, drop the samples further than kappa sigma from the fit, fit the survivors again, until nothing more is dropped: the remedy for
+ * samples a validity rule fixed before the fit cannot see (a highlight that does not clip, a cast shadow, an inter-reflection, a
+ * pixel whose map entry names the wrong face).  The inputs are a packed batch, as for brdf_hip_fit_batch_packed_dev, plus kappa,
+ * sigma_min and rounds.  No fit or statistics kernel of its own: the fits and the statistics are the packed entries'.
+ *   Round 0      every fit runs from d_p on all of its samples: the bytes of brdf_hip_fit_batch_packed_dev.
+ *   Settled      a fit that is refused (k < 3) or ends with ret < 0 is settled: it keeps those outputs and all of its samples.
+ *   Clip rounds  r = 1 ... rounds, for every fit that is not settled, with its k current samples at its current p:
+ *                  sumsq is stats[0] of brdf_hip_fit_stats_batch_packed_dev on the current sample set at p (the exact path, sums in
+ *                  fixed-order trees).  A sumsq that is not finite settles the fit with nothing clipped.
+ *                  sigma = fmax(sqrt(sumsq / (k - 3)), sigma_min) for k > 3; for k == 3, sigma = sigma_min.
+ *                  Sample i survives iff fabs(x_i - f_i(p)) <= kappa * sigma, f on the exact path (the reference's own pow
+ *                  expression, as the statistics pass evaluates it).  A NaN residual fails the comparison.
+ *                  No sample dropped: the fit is settled.  Fewer than 3 survivors: the clip is NOT applied and the fit is settled.
+ *                  Otherwise the survivors replace the fit's sample set, keeping their order -- clipping is monotone, a dropped
+ *                  sample never returns -- and the fit runs again from its current p: its p, info and ret become the bytes of
+ *                  brdf_hip_fit_batch_packed_dev on the survivors from that p, and rounds_used[s] = r.  A refit that ends with
+ *                  ret < 0 settles the fit with those outputs.  The loop ends early when every fit is settled.
+ *   Statistics   covar, stats and rank are the bytes of brdf_hip_fit_stats_batch_packed_dev at the returned p over the returned
+ *                sample set.
+ *   Invariant    every returned fit is a fit OF ITS RETURNED SAMPLE SET: p, info and ret are the packed call's bytes on that set
+ *                from the previous round's p, the statistics the packed pass's bytes at its own p.  rounds = 0, or kappa = +inf,
+ *                returns the bytes of the two packed entries, a mask of ones, kept = k and rounds_used = 0.
+ *   Outputs      d_info[S][10], d_ret[S], d_covar[S][9], d_stats[S][BRDF_STATS_SZ], d_rank[S], d_kept[S] (the samples of the fit's
+ *                returned set), d_rounds_used[S], d_mask[offsets[S] - offsets[0]] (1 = in the returned set, by the caller's
+ *                sample position: sample i of fit s is d_mask[offsets[s] - offsets[0] + i]): DEVICE, each may be NULL.
+ *   sigma_min    the floor of sigma: for 8-bit captures 1 / (255 sqrt(12)) = 0.0011320..., the quantisation's standard deviation,
+ *                is recommended -- a fit that matches its samples to the last bit must not clip on rounding.  0 is allowed.
+ *   Method       any BRDF_METHOD_*: the clip does not depend on it; the statistics use the method's Jacobian, as the packed pass does.
+ *   Waits        the call waits for `stream` as the packed calls do, once per fit and per statistics call (round 0, and per clip
+ *                round one statistics call and -- where a fit was clipped -- one refit; a last statistics call where the last
+ *                round refitted), once to read offsets[0] and offsets[S] (with rounds > 0 or a mask), and once per clip round for
+ *                one readback: is any fit still active?  With rounds > 0 or a mask it returns with the stream drained.
+ *   Memory       per sample position 38 bytes with rounds > 0 (the working batch of survivors 32, the fit of the position 4, the
+ *                round's decision 1, the mask 1 where d_mask is NULL), 32 bytes per surviving sample of the fits a round clips (its
+ *                refit batch) and 24 bytes per 256 positions; per fit about 250 bytes; and the packed calls' own workspace_bytes
+ *                (0: 1 GiB).  The caller's batch is never written.  rounds = 0 allocates nothing: it runs the packed calls' launches, one small
+ *                kernel for d_kept and d_rounds_used and, with a mask, one wait for the extent and one more small kernel for the ones.
+ *   Offsets      with rounds > 0 the device offsets must not descend (nor differ by more than INT_MAX): the clip rounds give every sample
+ *                position ONE fit.  Checked on the device and read back with the extent; such a batch is refused before round 0 writes
+ *                anything, where the packed entries -- and this one at rounds = 0 -- read the pair as a count of 0.
+ *   Checks       refused before any HIP call, under the entry's name: everything the packed entries refuse; a kappa that is not > 0
+ *                (a NaN included; +inf is allowed); a sigma_min that is negative or a NaN; rounds outside [0, 16].
+ *   Host entry   uploads, runs, downloads, synchronises; returns the number of fits with ret < 0.
+ * Not covered: clipping in the means capture (brdf_hip_fit_capture_means_dev: its fits see means, not samples), in the masked
+ * per-pixel capture (brdf_hip_fit_capture_masked_dev: 16-sample fits, too few to estimate sigma) and in the single-BRDF capture
+ * (brdf_hip_fit_capture_single_faces_dev); a MAD or another robust scale; dscl; a multi-GPU variant. */
+int brdf_hip_fit_batch_packed_clipped_dev(int method, int model, const double *d_angles, const double *d_x, const long long *d_offsets, int S,
+                                          double *d_p, const double *lb, const double *ub, int itmax, const double *opts, double kappa,
+                                          double sigma_min, int rounds, double *d_info, int *d_ret, double *d_covar, double *d_stats, int *d_rank,
+                                          int *d_kept, int *d_rounds_used, unsigned char *d_mask, long long workspace_bytes, void *stream);
+int brdf_hip_fit_batch_packed_clipped(int method, int model, const double *angles, const double *x, const long long *offsets, int S, double *p,
+                                      const double *lb, const double *ub, int itmax, const double *opts, double kappa, double sigma_min, int rounds,
+                                      double *info, int *ret, double *covar, double *stats, int *rank, int *kept, int *rounds_used,
+                                      unsigned char *mask, long long workspace_bytes);
+/* clip round `round` (1 ...) of the calling thread's last clipped call: the fits that were clipped and refitted in it, and the
+ * samples it dropped.  LM_ERROR for a round the call did not run (it stops after the first round that clips nothing). */
+int brdf_hip_last_clip_stats(int round, long long *active_fits, long long *clipped_samples);
 /* class cls (0: <= 16 samples ... 4: <= 4096, 5: above) of the calling thread's last packed call: its fits, the row stride of its
  * launches (0 for an empty class; class 5: the largest count) and its chunks (class 5: one run per fit).  LM_ERROR for another cls. */
 int brdf_hip_last_packed_stats(int cls, long long *fits, int *stride, int *chunks);
@@ -504,6 +562,25 @@ int brdf_hip_fit_capture_faces_dev(int model, const unsigned char *d_images, int
                                    double *d_brdf_surfaces, double *d_surface_info, int *d_surface_ret, double *d_surface_covar,
                                    double *d_surface_stats, int *d_surface_rank, int *d_surface_count, int *d_face_pixels, double *avg,
                                    long long *n_pixels, long long *n_faces, void *stream);
+
+/* brdf_hip_fit_capture_faces_dev with the sigma-clipped fit (brdf_hip_fit_batch_packed_clipped_dev: kappa, sigma_min, rounds as
+ * there) in place of the packed fit and statistics.  Everything in front of the fit -- grouping, cosines, validity rule, packing --
+ * and the scatter behind it are that entry's, and so are its arguments, maps, refusals (under this entry's name, plus the three new
+ * arguments') and waits, plus the clipped call's.
+ *   d_surface_count[nf][3]   keeps its meaning: the fit's candidate samples under the validity rule
+ *   d_surface_kept[nf][3]    the returned sample set's size (DEVICE, may be NULL)
+ *   d_surface_rounds[nf][3]  rounds_used (DEVICE, may be NULL)
+ * Faces no pixel carries stay untouched in both new maps.  The statistics maps are taken over the returned sample sets.  With
+ * rounds = 0 every map and scalar has the bytes of brdf_hip_fit_capture_faces_dev.  Memory: that entry's, plus the clipped call's
+ * per valid sample and per fit. */
+int brdf_hip_fit_capture_faces_clipped_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                           const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                           const double *view_origin, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
+                                           const double *opts, int v_min, int v_max, double cos_min, long long workspace_bytes,
+                                           double *d_brdf_surfaces, double *d_surface_info, int *d_surface_ret, double *d_surface_covar,
+                                           double *d_surface_stats, int *d_surface_rank, int *d_surface_count, int *d_face_pixels, double *avg,
+                                           long long *n_pixels, long long *n_faces, void *stream, double kappa, double sigma_min, int rounds,
+                                           int *d_surface_kept, int *d_surface_rounds);
 
 /* brdf_hip_fit_capture_faces_dev as a WEIGHTED fit of per-light means.  All pixels of a face share the face's cosines, so the model
  * values f_l(p) are the same for every pixel of the face, and with c_l valid values v_pl under light l and their mean m_l
