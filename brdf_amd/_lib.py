@@ -116,6 +116,11 @@ ABI = {
                                                  C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, C.c_int, C.c_int, C.c_double,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, D, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p]),
+    "brdf_hip_fit_capture_means_clipped_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, C.c_int, C.c_int, C.c_double,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, D, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p,
+                                                         C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "brdf_hip_fit_capture_single_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, D, D,
                                                   C.POINTER(C.c_longlong), C.c_void_p]),

@@ -852,6 +852,21 @@ int brdf_hip_fit_capture_means_dev(int model, const unsigned char *d_images, int
   return capture_means_run(a);
 }
 
+int brdf_hip_fit_capture_means_clipped_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                           const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                           const double *view_origin, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
+                                           const double *opts, int v_min, int v_max, double cos_min, double *d_brdf_surfaces, double *d_surface_info,
+                                           int *d_surface_ret, double *d_surface_covar, double *d_surface_stats, int *d_surface_rank, int *d_surface_count,
+                                           int *d_surface_lights, int *d_face_pixels, double *avg, long long *n_pixels, long long *n_faces, void *stream,
+                                           double kappa, double sigma_min, int rounds, int *d_surface_kept, int *d_surface_rounds,
+                                           unsigned char *d_surface_vlo, unsigned char *d_surface_vhi) {
+  const CaptureMeansClip clip = {{kappa, sigma_min, rounds, d_surface_kept, d_surface_rounds}, d_surface_vlo, d_surface_vhi};
+  const CaptureMeansArgs a = {{{CAPTURE_ARGS, v_min, v_max, cos_min, d_face_pixels, n_pixels, n_faces}, 0, d_brdf_surfaces, d_surface_info, d_surface_ret,
+                               d_surface_covar, d_surface_stats, d_surface_rank, d_surface_count, avg},
+                              d_surface_lights, &clip};
+  return capture_means_run(a);
+}
+
 int brdf_hip_fit_capture_single_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
                                     const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf,
                                     const double *leds, const double *view_origin, int rv_mode, const double *p0,

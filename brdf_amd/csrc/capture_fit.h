@@ -90,10 +90,17 @@ struct CaptureFacesArgs {
 };
 int capture_faces_run(const CaptureFacesArgs &a);  // refuses bad arguments before any HIP call
 
+// brdf_hip_fit_capture_means_clipped_dev: the sigma clip of the means capture (capture_means_clip.h) and its four maps
+struct CaptureMeansClip {
+  CaptureClip clip;
+  unsigned char *d_surface_vlo, *d_surface_vhi;  // [nf][3][L] or null: the returned set's grey-level interval per light
+};
+
 // brdf_hip_fit_capture_means_dev (capture_means.hip): the per-face capture as a weighted fit of per-light means
 struct CaptureMeansArgs {
   CaptureFacesArgs faces;  // brdf_hip_fit_capture_faces_dev's arguments (workspace_bytes unused; d_surface_count receives k)
   int *d_surface_lights;   // [nf][3] or null: the lights with a sample, the weighted fit's n
+  const CaptureMeansClip *clip = nullptr;  // null: brdf_hip_fit_capture_means_dev; otherwise the clipped entry, under its own name
 };
 int capture_means_run(const CaptureMeansArgs &a);  // refuses bad arguments before any HIP call
 

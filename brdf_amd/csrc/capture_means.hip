@@ -20,8 +20,12 @@
 //   fit, stats  weighted_fit_enqueue (dlevmar_bc_dif), weighted_stats_enqueue with extra_ss = within and nobs = k: sumsq, the
 //               covariance, sigma, rho and R^2 are those of the fit of all k samples
 //   scatter     rows (face, channel) in ascending order, block sums of p in a fixed order: capture_group.hip's, with the lights map
+// brdf_hip_fit_capture_means_clipped_dev (CaptureMeansArgs::clip) runs the clip rounds of capture_means_clip.hip between the fit and the
+// statistics, and scatters four more maps.
 #include "../../include/brdf_levmar.h"
 #include "capture_group.h"
+#include "capture_means_clip.h"
+#include "clip_fit.h"
 #include "fit_stats.h"
 #include "weighted_fit.h"
 
@@ -29,23 +33,14 @@ namespace brdf {
 
 namespace {
 
-constexpr const char *kWho = "brdf_hip_fit_capture_means_dev";
+constexpr const char *kWhoPlain = "brdf_hip_fit_capture_means_dev", *kWhoClipped = "brdf_hip_fit_capture_means_clipped_dev";
 constexpr int kMeansMaxL = 16;
 // a workgroup's kCT candidates touch at most kCT / L + 2 sorted pixels, so at most that many face ranks, each with 3 L words
 constexpr int kLocalWords = 3 * (kCT + 2 * kMeansMaxL);
 // c S2 - S1^2 <= (255 c)^2 must fit a signed 64-bit integer
 constexpr long long kMeansMaxPixels = 11000000;
 
-struct MeansCtx {
-  CandidateCtx cand;
-  // accumulators, word (channel * F + rank) * L + light
-  int *cnt;
-  unsigned long long *s1, *s2;
-  // the weighted batch: rows of stride L
-  double *angles, *x, *w, *within, *p;
-  int *lights, *nobs;
-  double p0[kM];
-};
+struct MeansCtx : MeansState {};  // (capture_means_clip.h)
 
 __global__ __launch_bounds__(kCT) void means_accumulate_kernel(MeansCtx c) {
   __shared__ int l_cnt[kLocalWords];
@@ -118,10 +113,13 @@ __global__ __launch_bounds__(kCT) void means_pack_kernel(MeansCtx c) {
 int capture_means_run(const CaptureMeansArgs &ma) {
   const CaptureFacesArgs &a = ma.faces;
   const CaptureArgs &cap = a.g.cap;
+  const CaptureClip *clip = ma.clip ? &ma.clip->clip : nullptr;
+  const char *kWho = clip ? kWhoClipped : kWhoPlain;
   // what the entry refuses before any HIP call
   if (capture_args_check(kWho, a.g, a.d_brdf_surfaces, "brdf_surfaces", kMeansMaxL,
                          " (the weighted fit's size class; brdf_hip_fit_capture_faces_dev takes L <= 64)") != 0)
     return kLmError;
+  if (clip && clip_spec_check(ClipSpec{clip->kappa, clip->sigma_min, clip->rounds}, kWho) != 0) return kLmError;
   (void)hipGetLastError();
   hipStream_t stream = cap.stream;
   const int L = cap.L;
@@ -174,23 +172,57 @@ int capture_means_run(const CaptureMeansArgs &ma) {
   const bool want_stats = a.d_surface_covar || a.d_surface_stats || a.d_surface_rank;
   FitResultBufs res;
   if (!take_fit_results(res, a, fits, kWho)) return kLmError;
+  // (the clip rounds read every fit's ret)
+  const bool rounds = clip && clip->rounds > 0;
+  DevBuf own_ret;
+  if (rounds && !res.ret.ptr && !take(own_ret, sizeof(int) * (size_t)fits, "the fits' ret", kWho)) return kLmError;
+  int *ret = res.ret.ptr ? res.ret.as<int>() : own_ret.as<int>();
   const WeightedFitArgs wf = {{BRDF_METHOD_BC_DIF, cap.model, angles.as<double>(), x.as<double>(), fits, L, p.as<double>(), cap.lb, cap.ub, cap.itmax, cap.opts,
-                               res.info.as<double>(), res.ret.as<int>(), stream, lights.as<int>()},
+                               res.info.as<double>(), ret, stream, lights.as<int>()},
                               w.as<double>()};
   if (weighted_fit_enqueue(wf, kWho) != 0) return kLmError;
-  if (want_stats && L >= kM) {
+
+  // ---- the clip rounds (capture_means_clip.hip): the intervals, the counts of round 0, rounds_used ----
+  DevBuf vlo, vhi, nobs0, rounds_used;
+  bool stats_fresh = false;
+  if (clip) {
+    if (!take(vlo, words, "the lights' lowest grey levels", kWho) || !take(vhi, words, "the lights' highest grey levels", kWho)) return kLmError;
+    if (means_clip_intervals(kWho, mc.cand, vlo.as<unsigned char>(), vhi.as<unsigned char>(), stream) != 0) return kLmError;
+  }
+  if (rounds) {
+    if (!take(nobs0, sizeof(int) * (size_t)fits, "the fits' unclipped sample counts", kWho) ||
+        !take(rounds_used, sizeof(int) * (size_t)fits, "the fits' rounds", kWho))
+      return kLmError;
+    CAPTURE_OK(kWho, hipMemcpyAsync(nobs0.ptr, nobs.ptr, sizeof(int) * (size_t)fits, hipMemcpyDeviceToDevice, stream));
+    CAPTURE_OK(kWho, hipMemsetAsync(rounds_used.ptr, 0, sizeof(int) * (size_t)fits, stream));
+    const MeansClipArgs ca = {kWho, mc, &cap, fits, clip->kappa, clip->sigma_min, clip->rounds, res.info.as<double>(), ret, res.covar.as<double>(),
+                              res.stats.as<double>(), res.rank.as<int>(), rounds_used.as<int>(), vlo.as<unsigned char>(), vhi.as<unsigned char>()};
+    if (means_clip_run(ca, &stats_fresh) != 0) return kLmError;
+  } else if (clip) {
+    clip_last_stats_set(ClipLastStats{});
+  }
+
+  // ---- the statistics at the returned p over the returned rows ----
+  if (want_stats && L >= kM && !stats_fresh) {
     const WeightedStatsArgs ws = {{BRDF_METHOD_BC_DIF, cap.model, angles.as<double>(), x.as<double>(), fits, L, p.as<double>(), cap.opts, res.covar.as<double>(),
                                    res.stats.as<double>(), res.rank.as<int>(), nullptr, 0, stream, lights.as<int>()},
                                   w.as<double>(), within.as<double>(), nobs.as<int>()};
     if (weighted_stats_enqueue(ws, kWho) != 0) return kLmError;
-  } else if (want_stats) {  // fewer than three lights: every fit is refused, there is nothing to take statistics of
+  } else if (want_stats && L < kM) {  // fewer than three lights: every fit is refused, there is nothing to take statistics of
     if (res.covar.ptr) CAPTURE_OK(kWho, hipMemsetAsync(res.covar.ptr, 0, sizeof(double) * kM * kM * (size_t)fits, stream));
     if (res.stats.ptr) CAPTURE_OK(kWho, hipMemsetAsync(res.stats.ptr, 0, sizeof(double) * kStatsSz * (size_t)fits, stream));
     if (res.rank.ptr) CAPTURE_OK(kWho, hipMemsetAsync(res.rank.ptr, 0, sizeof(int) * (size_t)fits, stream));
   }
 
-  // ---- scatter (capture_group.hip) ----
-  const ScatterArgs sc = {&a, &g, p.as<double>(), &res, nullptr, nobs.as<int>(), lights.as<int>(), ma.d_surface_lights};
+  // ---- scatter (capture_group.hip); `count` stays the unclipped sample count, `lights` is the returned set's ----
+  if (clip) {
+    if (clip_scatter_maps(kWho, g.face_list.as<int>(), (int)g.F, nobs.as<int>(), rounds_used.as<int>(), nullptr, clip->d_surface_kept, clip->d_surface_rounds,
+                          stream) != 0 ||
+        means_clip_scatter(kWho, g.face_list.as<int>(), (int)g.F, L, vlo.as<unsigned char>(), vhi.as<unsigned char>(), ma.clip->d_surface_vlo,
+                           ma.clip->d_surface_vhi, stream) != 0)
+      return kLmError;
+  }
+  const ScatterArgs sc = {&a, &g, p.as<double>(), &res, nullptr, rounds ? nobs0.as<int>() : nobs.as<int>(), lights.as<int>(), ma.d_surface_lights};
   return capture_scatter_run(kWho, sc);
 }
 

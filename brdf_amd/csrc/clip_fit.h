@@ -51,6 +51,7 @@ struct ClipLastStats {
   long long active[kClipMaxRounds], clipped[kClipMaxRounds];
 };
 ClipLastStats clip_last_stats();
+void clip_last_stats_set(const ClipLastStats &s);  // (capture_means_clip.hip records its rounds here)
 
 // rows (carried face, channel) of two [nf][3] int maps <- rows channel * F + face rank of the batch (either map may be null); enqueues.
 // d_kept null: the fits' counts by d_offsets; d_rounds null: 0 -- what a call with rounds = 0 returns, without its two arrays

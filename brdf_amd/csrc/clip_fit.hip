@@ -317,6 +317,7 @@ unsigned blocks_of(long long n) { return (unsigned)((n + kCT - 1) / kCT); }
 }  // namespace
 
 ClipLastStats clip_last_stats() { return g_clip_last; }
+void clip_last_stats_set(const ClipLastStats &s) { g_clip_last = s; }
 
 int clip_spec_check(const ClipSpec &c, const char *who) {
   if (!(c.kappa > 0.0) || !(c.sigma_min >= 0.0) || c.rounds < 0 || c.rounds > kClipMaxRounds) {

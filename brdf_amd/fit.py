@@ -882,6 +882,70 @@ def fit_capture_means(model: int, images, pixel_map, vertices, faces, face_norma
     return CaptureMeans(out.surfaces, out.info, out.ret, st, out.count, out.lights, out.face_pixels, avg, npx.value, nfc.value)
 
 
+class CaptureMeansClipped(NamedTuple):
+    """What fit_capture_means_clipped returns: CaptureMeans' fields and the clip's four maps."""
+    surfaces: object
+    info: object
+    ret: object
+    stats: FitStats | None  # over the returned sample sets
+    count: object        # [nf,3] int32: the fit's samples under the validity rule, before any clip
+    lights: object       # [nf,3] int32: the lights with a sample in the returned set
+    face_pixels: object
+    avg: np.ndarray
+    n_pixels: int
+    n_faces: int
+    kept: object         # [nf,3] int32: k of the returned set
+    rounds: object       # [nf,3] int32: the last clip round that refitted the fit (0: none)
+    vlo: object          # [nf,3,L] uint8: the returned set's grey-level interval per light of the capture, lowest level
+    vhi: object          # [nf,3,L] uint8: highest level (vlo = 1, vhi = 0: no level)
+
+
+def fit_capture_means_clipped(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, kappa: float, sigma_min: float,
+                              rounds: int, v_min: int = 0, v_max: int = 255, cos_min: float = -2.0, rv_mode: int = 0, p0=(0.5, 1.0, 1.0),
+                              lb=(0.0, 0.0, 0.0), ub=(100.0, 100.0, 100.0), itmax: int = 100, opts=None, want_stats: bool = True,
+                              validate: bool = True, out: CaptureMeansClipped | None = None) -> CaptureMeansClipped:
+    """fit_capture_means with sigma clipping (brdf_hip_fit_capture_means_clipped_dev; L <= 16): fit, drop the samples further than
+    kappa * sigma from the fit, fit the survivors' per-light means again from the current p, at most `rounds` times or until nothing
+    more is dropped.  All pixels of a face share its cosines, so a round's survivors under one light are an interval of grey levels:
+    the clip state is `vlo`, `vhi`, and a round accumulates the integer sums again under them -- clip_light_means is one round as
+    NumPy code, capture_light_means(v_lo=, v_hi=) the rows under given intervals.  sigma = max(sqrt(sumsq / (k - 3)), sigma_min) with
+    the full-sample sumsq of the weighted statistics pass (k == 3: sigma_min; SIGMA_MIN_8BIT is recommended); a fit that is refused,
+    ends with ret < 0, drops nothing or would keep fewer than 3 lights is settled and keeps its samples.  `count` stays the unclipped
+    sample count, `kept` and `lights` are the returned set's, `stats` are taken over it.  rounds = 0 or kappa = inf give
+    fit_capture_means' bytes in every map it has.  `out`: an earlier result (or one built by hand) whose tensors are written into."""
+    import torch
+    args, keep, nf = _capture_args(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, rv_mode, p0, lb, ub, itmax, opts,
+                                   validate)
+    dev = keep[0].device
+    L = int(keep[0].shape[0])
+
+    def z(*shape, dtype=torch.float64):
+        return torch.zeros((nf, *shape), dtype=dtype, device=dev)
+    if out is None:
+        i32, u8 = torch.int32, torch.uint8
+        out = CaptureMeansClipped(z(3, 3), z(3, 10), z(3, dtype=i32), _zero_stats((nf, 3), dev) if want_stats else None, z(3, dtype=i32), z(3, dtype=i32),
+                                  z(dtype=i32), None, 0, 0, z(3, dtype=i32), z(3, dtype=i32), z(3, L, dtype=u8), z(3, L, dtype=u8))
+    _require(not want_stats or out.stats is not None, "out: want_stats needs out.stats")
+    st = out.stats if want_stats else None
+    maps = [(out.surfaces, (nf, 3, 3), torch.float64), (out.info, (nf, 3, 10), torch.float64), (out.face_pixels, (nf,), torch.int32),
+            (out.vlo, (nf, 3, L), torch.uint8), (out.vhi, (nf, 3, L), torch.uint8)]
+    maps += [(t, (nf, 3), torch.int32) for t in (out.ret, out.count, out.lights, out.kept, out.rounds)]
+    if st is not None:
+        maps += [(st.covar, (nf, 3, 3, 3), torch.float64), (st.stats, (nf, 3, 8), torch.float64), (st.rank, (nf, 3), torch.int32)]
+    for t, shape, dtype in maps:
+        _require(t.is_cuda and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(),
+                 f"out: contiguous CUDA {dtype} {list(shape)} tensors on the capture's device")
+    avg = np.zeros(3)
+    npx, nfc = C.c_longlong(0), C.c_longlong(0)
+    _call("brdf_hip_fit_capture_means_clipped_dev", dev, *args, int(v_min), int(v_max), float(cos_min), out.surfaces.data_ptr(), out.info.data_ptr(),
+          out.ret.data_ptr(), None if st is None else st.covar.data_ptr(), None if st is None else st.stats.data_ptr(),
+          None if st is None else st.rank.data_ptr(), out.count.data_ptr(), out.lights.data_ptr(), out.face_pixels.data_ptr(), _dptr(avg),
+          C.byref(npx), C.byref(nfc), _STREAM, float(kappa), float(sigma_min), int(rounds), out.kept.data_ptr(), out.rounds.data_ptr(),
+          out.vlo.data_ptr(), out.vhi.data_ptr())
+    return CaptureMeansClipped(out.surfaces, out.info, out.ret, st, out.count, out.lights, out.face_pixels, avg, npx.value, nfc.value, out.kept,
+                               out.rounds, out.vlo, out.vhi)
+
+
 class LightMeans(NamedTuple):
     """What capture_light_means returns: the weighted batch of fit_capture_means, rows of stride L (NumPy)."""
     angles: np.ndarray       # [fits,3,L] float64: the face's cosines at the lights with a sample, ascending; NaN behind counts
@@ -895,11 +959,14 @@ class LightMeans(NamedTuple):
     face_pixels: np.ndarray  # [nf] int32
 
 
-def capture_light_means(images, pixel_map, face_angles, model: int, *, v_min: int = 0, v_max: int = 255, cos_min: float = -2.0) -> LightMeans:
+def capture_light_means(images, pixel_map, face_angles, model: int, *, v_min: int = 0, v_max: int = 255, cos_min: float = -2.0, v_lo=None,
+                        v_hi=None) -> LightMeans:
     """The host twin of fit_capture_means' accumulation (NumPy, no device): its definition as code.  Arguments, fits (ascending face,
     then channel), candidates and validity rule as group_capture_samples.  Per fit and light l with c_l > 0 valid values v:
     x_l = sum v / (255 c_l), w_l = c_l; the lights with a sample in ascending order at the front of rows of stride L; k = sum c_l;
-    within = sum_l (c_l sum v^2 - (sum v)^2) / (65025 c_l), the numerator in integers, added in ascending light order."""
+    within = sum_l (c_l sum v^2 - (sum v)^2) / (65025 c_l), the numerator in integers, added in ascending light order.
+    v_lo, v_hi ([fits,L], optional, both or neither): the grey-level intervals of fit_capture_means_clipped -- a valid value v under
+    light l is a sample iff v_lo[s, l] <= v <= v_hi[s, l]; without them every valid value is."""
     images, pixel_map = np.asarray(images), np.asarray(pixel_map)
     face_angles = np.ascontiguousarray(face_angles, dtype=np.float64)
     _require(images.ndim == 4 and images.shape[3] == 3 and images.dtype == np.uint8 and pixel_map.shape == images.shape[1:3],
@@ -917,6 +984,10 @@ def capture_light_means(images, pixel_map, face_angles, model: int, *, v_min: in
         if ys.size:
             values[f] = images[:, H - 1 - ys, xs, :].astype(np.int64)
     fits = 3 * len(values)
+    _require((v_lo is None) == (v_hi is None), "v_lo and v_hi: both or neither")
+    if v_lo is not None:
+        v_lo, v_hi = np.asarray(v_lo).astype(np.int64), np.asarray(v_hi).astype(np.int64)
+        _require(v_lo.shape == (fits, L) and v_hi.shape == (fits, L), "v_lo, v_hi [fits,L]")
     angles, x, w = np.full((fits, 3, L), np.nan), np.full((fits, L), np.nan), np.full((fits, L), np.nan)
     counts, k, within = np.zeros(fits, dtype=np.int32), np.zeros(fits, dtype=np.int32), np.zeros(fits)
     fit_face, fit_channel = np.zeros(fits, dtype=np.int32), np.zeros(fits, dtype=np.int32)
@@ -929,6 +1000,8 @@ def capture_light_means(images, pixel_map, face_angles, model: int, *, v_min: in
             for l in range(L):
                 v = values[f][l, :, ch]
                 v = v[(v >= v_min) & (v <= v_max)] if cos_ok[l] else v[:0]
+                if v_lo is not None:
+                    v = v[(v >= v_lo[s, l]) & (v <= v_hi[s, l])]
                 c = int(v.size)
                 if c == 0:
                     continue
@@ -942,6 +1015,74 @@ def capture_light_means(images, pixel_map, face_angles, model: int, *, v_min: in
             counts[s] = n
             s += 1
     return LightMeans(angles, x, w, counts, k, within, fit_face, fit_channel, face_pixels)
+
+
+def initial_light_intervals(face_angles, fit_face, model: int, *, v_min: int = 0, v_max: int = 255, cos_min: float = -2.0):
+    """The intervals fit_capture_means_clipped starts from (NumPy): per fit of fit_face [fits] and light, [v_min, v_max] clamped to
+    0 ... 255 where every plane the model reads is > cos_min (a NaN is not), and the empty interval lo = 1, hi = 0 elsewhere.
+    Returns (v_lo, v_hi), uint8 [fits,L]."""
+    face_angles = np.asarray(face_angles, dtype=np.float64)
+    reads = [True, model != MODEL_PHONG, model != MODEL_BLINN_PHONG]
+    a = face_angles[np.asarray(fit_face, dtype=np.int64)]  # [fits,3,L]
+    with np.errstate(invalid="ignore"):
+        cos_ok = np.all([a[:, j, :] > cos_min for j in range(3) if reads[j]], axis=0)
+    lo, hi = int(np.clip(v_min, 0, 255)), int(np.clip(v_max, 0, 255))
+    return np.where(cos_ok, lo, 1).astype(np.uint8), np.where(cos_ok, hi, 0).astype(np.uint8)
+
+
+def clip_light_means(images, pixel_map, face_angles, model: int, p, sumsq, ret, v_lo, v_hi, *, kappa: float, sigma_min: float, v_min: int = 0,
+                     v_max: int = 255, cos_min: float = -2.0):
+    """ONE clip round of fit_capture_means_clipped's definition, as NumPy code on the host (no device).  The capture and the rule as
+    capture_light_means; v_lo, v_hi [fits,L] the fits' CURRENT intervals (initial_light_intervals before the first round), p [fits,3]
+    their current parameters, sumsq [fits] the weighted statistics pass's stats[:, 0] at p over the current rows with extra_ss = within
+    and nobs = k, ret [fits] the fits' ret.  Returns (new v_lo, new v_hi, settled [fits] bool).  For a fit with ret < 0, fewer than 3
+    lights with a sample or a sumsq that is not finite: settled, its intervals as they came.  Otherwise sigma = max(sqrt(sumsq /
+    (k - 3)), sigma_min) (k == 3: sigma_min), grey level v under light l survives iff |v / 255.0 - f_l(p)| <= kappa * sigma (a NaN
+    does not), and a light's new interval runs from the smallest to the largest surviving v inside the old one (empty, lo = 1 and
+    hi = 0, if none survives).  No sample dropped, or fewer than 3 lights keep a sample: settled, the intervals as they came.  The
+    caller marks settled fits and never passes them as unsettled again: here every fit given is looked at."""
+    from . import synth
+    face_angles = np.ascontiguousarray(face_angles, dtype=np.float64)
+    v_lo, v_hi = np.asarray(v_lo), np.asarray(v_hi)
+    cur = capture_light_means(images, pixel_map, face_angles, model, v_min=v_min, v_max=v_max, cos_min=cos_min, v_lo=v_lo, v_hi=v_hi)
+    fits, L = v_lo.shape
+    p, sumsq, ret = np.asarray(p, dtype=np.float64), np.asarray(sumsq, dtype=np.float64), np.asarray(ret)
+    _require(p.shape == (fits, 3) and sumsq.shape == (fits,) and ret.shape == (fits,), "p [fits,3], sumsq [fits], ret [fits]")
+    new_lo, new_hi = v_lo.astype(np.uint8).copy(), v_hi.astype(np.uint8).copy()
+    settled = np.ones(fits, dtype=bool)
+    for s in range(fits):
+        k = int(cur.k[s])
+        if ret[s] < 0 or cur.counts[s] < 3 or not np.isfinite(sumsq[s]):
+            continue
+        a = face_angles[cur.fit_face[s]]  # [3,L]: by the capture's light index
+        grey = np.arange(256)
+        with np.errstate(all="ignore"):
+            sigma = max(float(np.sqrt(sumsq[s] / (k - 3))), float(sigma_min)) if k > 3 else float(sigma_min)
+            f = synth.model_value(model, p[s], a[0], a[1], a[2])  # [L]
+            ok = np.abs(grey[None, :] / 255.0 - f[:, None]) <= np.float64(kappa) * np.float64(sigma)  # [L,256] (False for a NaN)
+        ok &= (grey[None, :] >= v_lo[s].astype(np.int64)[:, None]) & (grey[None, :] <= v_hi[s].astype(np.int64)[:, None])
+        any_ok = ok.any(axis=1)
+        lo = np.where(any_ok, ok.argmax(axis=1), 1)
+        hi = np.where(any_ok, 255 - ok[:, ::-1].argmax(axis=1), 0)
+        sub = _light_sums(images, pixel_map, face_angles, model, cur.fit_face[s], cur.fit_channel[s], lo, hi, v_min, v_max, cos_min)
+        if int(sub.sum()) >= k or int((sub > 0).sum()) < 3:
+            continue
+        new_lo[s], new_hi[s] = lo, hi
+        settled[s] = False
+    return new_lo, new_hi, settled
+
+
+def _light_sums(images, pixel_map, face_angles, model, face, channel, lo, hi, v_min, v_max, cos_min):
+    """the samples per light of fit (face, channel) under the rule and the intervals lo, hi [L]"""
+    images, pixel_map = np.asarray(images), np.asarray(pixel_map)
+    L, H = images.shape[:2]
+    reads = [True, model != MODEL_PHONG, model != MODEL_BLINN_PHONG]
+    with np.errstate(invalid="ignore"):
+        cos_ok = np.all([face_angles[face, j, :] > cos_min for j in range(3) if reads[j]], axis=0)
+    ys, xs = np.nonzero(pixel_map == face)
+    v = images[:, H - 1 - ys, xs, channel].astype(np.int64)  # [L, pixels]
+    ok = (v >= v_min) & (v <= v_max) & cos_ok[:, None] & (v >= np.asarray(lo)[:, None]) & (v <= np.asarray(hi)[:, None])
+    return ok.sum(axis=1)
 
 
 def fit_capture_single(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, rv_mode: int = 0,

@@ -410,7 +410,8 @@ int brdf_hip_fit_stats_batch_packed(int method, int model, const double *angles,
  *   Checks       refused before any HIP call, under the entry's name: everything the packed entries refuse; a kappa that is not > 0
  *                (a NaN included; +inf is allowed); a sigma_min that is negative or a NaN; rounds outside [0, 16].
  *   Host entry   uploads, runs, downloads, synchronises; returns the number of fits with ret < 0.
- * Not covered: clipping in the means capture (brdf_hip_fit_capture_means_dev: its fits see means, not samples), in the masked
+ * Not covered: clipping in the means capture by this entry (brdf_hip_fit_capture_means_dev: its fits see means, not samples --
+ * brdf_hip_fit_capture_means_clipped_dev below clips it by grey-level intervals), in the masked
  * per-pixel capture (brdf_hip_fit_capture_masked_dev: 16-sample fits, too few to estimate sigma) and in the single-BRDF capture
  * (brdf_hip_fit_capture_single_faces_dev); a MAD or another robust scale; dscl; a multi-GPU variant. */
 int brdf_hip_fit_batch_packed_clipped_dev(int method, int model, const double *d_angles, const double *d_x, const long long *d_offsets, int S,
@@ -617,6 +618,58 @@ int brdf_hip_fit_capture_means_dev(int model, const unsigned char *d_images, int
                                    const double *opts, int v_min, int v_max, double cos_min, double *d_brdf_surfaces, double *d_surface_info,
                                    int *d_surface_ret, double *d_surface_covar, double *d_surface_stats, int *d_surface_rank, int *d_surface_count,
                                    int *d_surface_lights, int *d_face_pixels, double *avg, long long *n_pixels, long long *n_faces, void *stream);
+
+/* brdf_hip_fit_capture_means_dev with sigma clipping: the fast capture and the robust one in one entry.  All pixels of a face share
+ * the face's cosines, so whether a sample survives a clip round depends on (fit, light, grey level v) alone: a round's survivors
+ * under one light are an interval of grey levels, "a dropped sample never returns" is an intersection of intervals, and the whole
+ * clip state is two bytes per (fit, light).  A round accumulates the integer sums again under the intervals: no per-candidate array,
+ * no float atomics.  This is the definition of brdf_hip_fit_batch_packed_clipped_dev, restated for means (kappa, sigma_min, rounds
+ * as there; brdf_amd.clip_light_means is one round of it as NumPy code).  A fit is (carried face, channel); candidates and validity
+ * rule are brdf_hip_fit_capture_means_dev's.
+ *   Intervals    per (fit, light l) an interval [lo_l, hi_l] of grey levels: at the start [v_min, v_max] clamped to 0 ... 255 for a
+ *                light whose cosines pass the rule, empty -- written lo = 1, hi = 0 -- for a light whose cosines fail.  The fit's
+ *                current sample set: the valid candidates with lo_l <= v <= hi_l.
+ *   Round 0      brdf_hip_fit_capture_means_dev's fit, with its bytes.
+ *   Settled      a fit that is refused (fewer than 3 lights with a sample) or ends with ret < 0 is settled: it keeps its outputs and
+ *                its samples.
+ *   Clip rounds  r = 1 ... rounds, for every fit that is not settled, at its current p:
+ *                  sumsq is stats[0] of brdf_hip_fit_stats_batch_weighted_dev on the current rows with extra_ss = within and
+ *                  nobs = k: the full-sample sum of squares.  A sumsq that is not finite settles the fit with nothing clipped.
+ *                  sigma = fmax(sqrt(sumsq / (k - 3)), sigma_min) for k > 3; for k == 3, sigma = sigma_min.
+ *                  Grey level v under light l survives iff fabs(v / 255.0 - f_l(p)) <= kappa * sigma, f on the exact path (the
+ *                  reference's own pow expression, as the statistics pass evaluates it).  A NaN residual fails the comparison.
+ *                  The new interval of a light runs from the smallest to the largest surviving v inside the old one; it is empty
+ *                  if none survives.
+ *                  No sample dropped: the fit is settled.  Fewer than 3 lights keep a sample: the clip is NOT applied, the
+ *                  intervals stay as they were, and the fit is settled.
+ *                  Otherwise the intervals are adopted; count, sum v and sum v^2 per light, means, weights, within, k and the
+ *                  lights are formed again from the survivors -- the integer arithmetic and the pack of round 0 --, the fit runs
+ *                  again from its current p: its p, info and ret become the bytes of brdf_hip_fit_batch_weighted_dev on those rows
+ *                  from that p, and rounds = r.  The loop ends early when every fit is settled.
+ *   Statistics   the bytes of brdf_hip_fit_stats_batch_weighted_dev at the returned p over the returned rows, with their within and k.
+ *   Maps         brdf_hip_fit_capture_means_dev's, and four more (DEVICE, each may be NULL):
+ *                d_surface_kept[nf][3]      k of the returned set           d_surface_rounds[nf][3]   the last round that refitted
+ *                d_surface_vlo[nf][3][L], d_surface_vhi[nf][3][L]  (unsigned char) the returned intervals, by the capture's own light
+ *                index: with the images and the rule they rebuild the keep mask, as the packed entry's d_mask does.
+ *                d_surface_count stays the UNCLIPPED sample count; d_surface_lights is the returned set's.  Faces no pixel carries
+ *                are left untouched in every map.
+ *   rounds = 0, or kappa = +inf: brdf_hip_fit_capture_means_dev's bytes in every map it has; kept = count, rounds 0, the initial
+ *                intervals.
+ *   Waits        that entry's, and one per clip round for one readback: is any fit still active?  Only the fits a round clipped
+ *                are fitted again, as a dense batch.  brdf_hip_last_clip_stats reports the rounds.
+ *   Memory       that entry's, plus per (carried face, channel, light) 4 bytes of intervals and, with rounds > 0, 40 bytes of the
+ *                dense refit batch; per fit about 200 bytes.
+ *   Refused      before any HIP call, under this entry's name: what brdf_hip_fit_capture_means_dev refuses (L outside [1, 16]
+ *                included), a kappa that is not > 0 (+inf is allowed), a sigma_min that is negative or a NaN, rounds outside [0, 16].
+ * Not covered: clipping in the masked per-pixel and the single-BRDF captures, L > 16, a MAD scale, dscl, a multi-GPU variant. */
+int brdf_hip_fit_capture_means_clipped_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                           const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                           const double *view_origin, int rv_mode, const double *p0, const double *lb, const double *ub, int itmax,
+                                           const double *opts, int v_min, int v_max, double cos_min, double *d_brdf_surfaces, double *d_surface_info,
+                                           int *d_surface_ret, double *d_surface_covar, double *d_surface_stats, int *d_surface_rank, int *d_surface_count,
+                                           int *d_surface_lights, int *d_face_pixels, double *avg, long long *n_pixels, long long *n_faces, void *stream,
+                                           double kappa, double sigma_min, int rounds, int *d_surface_kept, int *d_surface_rounds,
+                                           unsigned char *d_surface_vlo, unsigned char *d_surface_vhi);
 
 /* Replaces CBRDFdata::CalcBRDFEquation_SingleBRDF (brdfdata.cpp:1138-1186) with SolveEquation_SingleBRDF (:992-1062): ONE
  * {kd, ks, n} per colour channel for the whole object, fitted with dlevmar_bc_dif to the L samples of every face the pixel
