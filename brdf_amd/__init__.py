@@ -13,4 +13,6 @@ from .fit import (METHOD_BC_DER, METHOD_BC_DIF, METHOD_DER, METHOD_DIF, MODEL_BL
                   fit_batch_weighted, fit_stats_batch_weighted, CaptureMeans, LightMeans, fit_capture_means, capture_light_means,
                   CaptureSingleFaces, SingleSamples, fit_capture_single_faces, group_capture_single_samples,
                   ClippedFit, CaptureFacesClipped, SIGMA_MIN_8BIT, fit_batch_packed_clipped, fit_capture_faces_clipped, clip_samples, last_clip_stats,
-                  CaptureMeansClipped, fit_capture_means_clipped, clip_light_means, initial_light_intervals)
+                  CaptureMeansClipped, fit_capture_means_clipped, clip_light_means, initial_light_intervals,
+                  FaceResiduals, CaptureLabelled, CaptureMaterials, LabelSamples, capture_face_residuals, fit_capture_labelled, fit_capture_materials,
+                  group_capture_label_samples, assign_materials, seed_materials)

@@ -128,6 +128,21 @@ ABI = {
                                                         C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, C.c_int, C.c_int, C.c_double,
                                                         D, D, I, D, D, I, C.POINTER(C.c_longlong), C.c_void_p, C.c_void_p, C.c_void_p,
                                                         C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_void_p]),
+    "brdf_hip_capture_face_residuals_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_int, D, D, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                                      C.c_void_p]),
+    "brdf_hip_fit_capture_labelled_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_int, D, D, C.c_int, D, D, C.c_int, D, C.c_int, C.c_int, C.c_double,
+                                                    C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong),
+                                                    C.POINTER(C.c_longlong), C.c_void_p]),
+    "brdf_hip_fit_capture_materials_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_int, D, D, C.c_int, D, D, C.c_int, D, C.c_int, C.c_int, C.c_double,
+                                                     C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, I, I, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                                     C.POINTER(C.c_longlong), C.c_void_p]),
     "brdf_hip_device_count": (C.c_int, []),
     "brdf_hip_last_error": (C.c_char_p, []),
     "brdf_hip_last_fit_launches": (C.c_longlong, []),

@@ -17,6 +17,7 @@
 #include "../../include/brdf_levmar.h"
 #include "batch_fit.h"
 #include "capture_fit.h"
+#include "capture_materials.h"
 #include "fit_host.h"
 #include "fit_stats.h"
 #include "clip_fit.h"
@@ -887,6 +888,46 @@ int brdf_hip_fit_capture_single_faces_dev(int model, const unsigned char *d_imag
   return capture_single_faces_run(a);
 }
 
+// the materials entries (capture_materials.h) read no p0: their starting points are the materials
+#define CAPTURE_ARGS_NO_START(lb_, ub_, itmax_, opts_) \
+  {model, d_images, L, H, W, d_pixel_map, d_vertices, d_faces, d_face_normals, nf, leds, view_origin, rv_mode, nullptr, lb_, ub_, itmax_, opts_, \
+   static_cast<hipStream_t>(stream)}
+
+int brdf_hip_capture_face_residuals_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                        const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                        const double *view_origin, int rv_mode, int v_min, int v_max, double cos_min, const double *d_materials, int M,
+                                        double *d_face_sumsq, int *d_face_count, int *d_face_pixels, long long *n_pixels, long long *n_faces,
+                                        void *stream) {
+  const CaptureResidualsArgs a = {{CAPTURE_ARGS_NO_START(nullptr, nullptr, 0, nullptr), v_min, v_max, cos_min, d_face_pixels, n_pixels, n_faces}, d_materials, M,
+                                  d_face_sumsq, d_face_count};
+  return capture_face_residuals_run(a);
+}
+
+int brdf_hip_fit_capture_labelled_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                      const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                      const double *view_origin, int rv_mode, const double *lb, const double *ub, int itmax, const double *opts, int v_min,
+                                      int v_max, double cos_min, long long workspace_bytes, const int *d_face_label, int K, double *d_materials,
+                                      double *d_info, int *d_ret, double *d_covar, double *d_stats, int *d_rank, int *d_count, int *d_label_faces,
+                                      int *d_face_pixels, long long *n_pixels, long long *n_faces, void *stream) {
+  const CaptureLabelledArgs a = {{CAPTURE_ARGS_NO_START(lb, ub, itmax, opts), v_min, v_max, cos_min, d_face_pixels, n_pixels, n_faces}, workspace_bytes,
+                                 const_cast<int *>(d_face_label), K, d_materials, d_info, d_ret, d_covar, d_stats, d_rank, d_count, d_label_faces};
+  return capture_labelled_run(a);
+}
+
+int brdf_hip_fit_capture_materials_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                       const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                       const double *view_origin, int rv_mode, const double *lb, const double *ub, int itmax, const double *opts, int v_min,
+                                       int v_max, double cos_min, long long workspace_bytes, int K, int rounds, double *d_materials, int *d_face_label,
+                                       double *d_face_sumsq, int *d_face_count, double *d_info, int *d_ret, double *d_covar, double *d_stats, int *d_rank,
+                                       int *d_count, int *d_label_faces, int *d_face_pixels, int *rounds_used, int *settled, long long *changed,
+                                       long long *n_pixels, long long *n_faces, void *stream) {
+  const CaptureMaterialsArgs a = {{{CAPTURE_ARGS_NO_START(lb, ub, itmax, opts), v_min, v_max, cos_min, d_face_pixels, n_pixels, n_faces}, workspace_bytes,
+                                   d_face_label, K, d_materials, d_info, d_ret, d_covar, d_stats, d_rank, d_count, d_label_faces},
+                                  rounds, d_face_sumsq, d_face_count, rounds_used, settled, changed};
+  return capture_materials_run(a);
+}
+
+#undef CAPTURE_ARGS_NO_START
 #undef CAPTURE_ARGS
 
 int brdf_hip_device_count(void) {

@@ -119,4 +119,37 @@ struct CaptureSingleFacesArgs {
 };
 int capture_single_faces_run(const CaptureSingleFacesArgs &a);  // refuses bad arguments before any HIP call; the channels with ret < 0
 
+// brdf_hip_capture_face_residuals_dev (capture_materials.hip): the carried faces' sums of squared residuals against M materials
+struct CaptureResidualsArgs {
+  CaptureGrouped g;           // (p0, lb, ub, itmax, opts unused: no fit)
+  const double *d_materials;  // [M][3][3], required
+  int M;
+  double *d_face_sumsq;       // [nf][M][3] or null
+  int *d_face_count;          // [nf][3] or null
+};
+
+// brdf_hip_fit_capture_labelled_dev (capture_materials.hip): one fit per (label, channel) over the faces that carry the label
+struct CaptureLabelledArgs {
+  CaptureGrouped g;           // (p0 unused: the materials are the starting points)
+  long long workspace_bytes;  // the packed calls'
+  int *d_face_label;          // [nf], required, read only here; outside [0, K): the face takes part in nothing
+  int K;
+  double *d_materials;        // [K][3][3] in/out, required
+  double *d_info;             // [K][3][10] or null
+  int *d_ret;                 // [K][3] or null
+  double *d_covar, *d_stats;  // [K][3][9], [K][3][kStatsSz] or null
+  int *d_rank, *d_count;      // [K][3] or null
+  int *d_label_faces;         // [K] or null: the carried faces of the label
+};
+
+// brdf_hip_fit_capture_materials_dev (capture_materials.hip): assign, refit, until no label moves
+struct CaptureMaterialsArgs {
+  CaptureLabelledArgs fit;  // d_face_label: written, [nf], required
+  int rounds;               // refits at most
+  double *d_face_sumsq;     // [nf][3] or null: against the face's own material
+  int *d_face_count;        // [nf][3] or null
+  int *rounds_used, *settled;  // host or null
+  long long *changed;          // host [rounds + 1] or null: the faces whose label changed, per assignment (-1: no such assignment)
+};
+
 }  // namespace brdf

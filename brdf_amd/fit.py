@@ -1182,6 +1182,248 @@ def group_capture_single_samples(images, pixel_map, face_angles, model: int, *, 
     return SingleSamples(tuple(channels), carried, face_pixels)
 
 
+# ---- K materials per object: residuals against M materials, one fit per (label, channel), Lloyd's iteration around the two ----------
+def _materials_tensor(materials, dev, torch):
+    """[M,3,3] float64 on `dev`: the caller's contiguous CUDA tensor itself (the labelled entries write into it), or an upload"""
+    if not torch.is_tensor(materials):
+        materials = torch.from_numpy(np.ascontiguousarray(materials, dtype=np.float64)).to(dev)
+    _require(materials.is_cuda and materials.device == dev and materials.dtype == torch.float64 and materials.dim() == 3
+             and tuple(materials.shape[1:]) == (3, 3) and materials.shape[0] >= 1 and materials.is_contiguous(),
+             "materials: [M,3,3] float64 (material, channel, parameter), contiguous, on the capture's device")
+    return materials
+
+
+class FaceResiduals(NamedTuple):
+    """What capture_face_residuals returns (CUDA tensors and the host scalars)."""
+    face_sumsq: object   # [nf,M,3] float64
+    face_count: object   # [nf,3] int32
+    face_pixels: object  # [nf] int32
+    n_pixels: int
+    n_faces: int
+
+
+def capture_face_residuals(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, materials, *, v_min: int = 0,
+                           v_max: int = 255, cos_min: float = -2.0, rv_mode: int = 0, validate: bool = True,
+                           out: FaceResiduals | None = None) -> FaceResiduals:
+    """The carried faces' sums of squared residuals against M candidate materials in one read of the samples
+    (brdf_hip_capture_face_residuals_dev).  Capture and validity rule as fit_capture_single_faces; materials [M,3,3] (material, channel,
+    {kd, ks, n}), a CUDA tensor or NumPy.  face_sumsq[f, m, c] is the sum over the face's valid samples of channel c of
+    (x - f(materials[m, c]))^2 with fit_capture_single_faces' summation: column m has the bytes that call writes to its face_sumsq when
+    its single_brdf equals materials[m], whatever M is and wherever m stands.  A sum that is not finite is stored as it comes.  Faces no
+    pixel carries keep what the maps held: zeros, or the values of `out`."""
+    import torch
+    args, keep, nf = _capture_args(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, rv_mode, None, None, None, 0, None,
+                                   validate)
+    dev = keep[0].device
+    materials = _materials_tensor(materials, dev, torch)
+    M = int(materials.shape[0])
+    if out is None:
+        out = FaceResiduals(torch.zeros((nf, M, 3), dtype=torch.float64, device=dev), torch.zeros((nf, 3), dtype=torch.int32, device=dev),
+                            torch.zeros((nf,), dtype=torch.int32, device=dev), 0, 0)
+    for t, shape, dtype in ((out.face_sumsq, (nf, M, 3), torch.float64), (out.face_count, (nf, 3), torch.int32), (out.face_pixels, (nf,), torch.int32)):
+        _require(t.is_cuda and t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(),
+                 f"out: contiguous CUDA {dtype} {list(shape)} tensors on the capture's device")
+    npx, nfc = C.c_longlong(0), C.c_longlong(0)
+    _call("brdf_hip_capture_face_residuals_dev", dev, *args[:13], int(v_min), int(v_max), float(cos_min), materials.data_ptr(), M,
+          out.face_sumsq.data_ptr(), out.face_count.data_ptr(), out.face_pixels.data_ptr(), C.byref(npx), C.byref(nfc), _STREAM)
+    return FaceResiduals(out.face_sumsq, out.face_count, out.face_pixels, npx.value, nfc.value)
+
+
+class CaptureLabelled(NamedTuple):
+    """What fit_capture_labelled returns: rows [label, channel] (CUDA tensors) and the host scalars."""
+    materials: object    # [K,3,3] float64: {kd, ks, n} per label and channel
+    info: object         # [K,3,10] float64
+    ret: object          # [K,3] int32
+    stats: FitStats | None  # covar [K,3,3,3], stats [K,3,8], rank [K,3]; None without want_stats
+    count: object        # [K,3] int32: the samples of the fit
+    label_faces: object  # [K] int32: the carried faces of the label
+    face_pixels: object  # [nf] int32
+    n_pixels: int
+    n_faces: int
+
+
+def _labelled_maps(K, nf, dev, want_stats, torch):
+    i32 = torch.int32
+    return (torch.zeros((K, 3, 10), dtype=torch.float64, device=dev), torch.zeros((K, 3), dtype=i32, device=dev),
+            _zero_stats((K, 3), dev) if want_stats else None, torch.zeros((K, 3), dtype=i32, device=dev), torch.zeros((K,), dtype=i32, device=dev),
+            torch.zeros((nf,), dtype=i32, device=dev))
+
+
+def fit_capture_labelled(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, labels, materials, *, v_min: int = 0,
+                         v_max: int = 255, cos_min: float = -2.0, rv_mode: int = 0, lb=(0.0, 0.0, 0.0), ub=(100.0, 100.0, 100.0), itmax: int = 100,
+                         opts=None, workspace_bytes: int = 0, want_stats: bool = True, validate: bool = True) -> CaptureLabelled:
+    """ONE fit per (label, channel) over the valid samples of the faces that carry the label (brdf_hip_fit_capture_labelled_dev).
+    labels [nf] int32 (CUDA tensor or NumPy): a face whose label is outside [0, K) takes part in nothing.  materials [K,3,3]: the
+    starting points; a contiguous CUDA tensor is overwritten with the results, as fit_batch_packed's p0 is.  Fit (k, c)'s samples are
+    the carried faces with label k in ascending face index, a face's pixels in the reference's walk, the lights inside a pixel, those
+    the rule leaves for channel c -- group_capture_label_samples is this definition as code -- and the 3 K fits are rows c * K + k of
+    one packed batch: every map has the bytes fit_batch_packed / fit_stats_batch_packed give for that batch from the same starts.
+    Fewer than 3 samples: ret -1, zero info, the material untouched, rank 0.  The call waits for the stream."""
+    import torch
+    args, keep, nf = _capture_args(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, rv_mode, None, lb, ub, itmax, opts,
+                                   validate)
+    dev = keep[0].device
+    materials = _materials_tensor(materials, dev, torch)
+    K = int(materials.shape[0])
+    if not torch.is_tensor(labels):
+        labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(dev)
+    _require(labels.is_cuda and labels.device == dev and labels.dtype == torch.int32 and tuple(labels.shape) == (nf,) and labels.is_contiguous(),
+             "labels: [nf] int32, contiguous, on the capture's device")
+    info, ret, st, count, label_faces, face_pixels = _labelled_maps(K, nf, dev, want_stats, torch)
+    npx, nfc = C.c_longlong(0), C.c_longlong(0)
+    _call("brdf_hip_fit_capture_labelled_dev", dev, *args[:13], *args[14:18], int(v_min), int(v_max), float(cos_min), int(workspace_bytes),
+          labels.data_ptr(), K, materials.data_ptr(), info.data_ptr(), ret.data_ptr(), None if st is None else st.covar.data_ptr(),
+          None if st is None else st.stats.data_ptr(), None if st is None else st.rank.data_ptr(), count.data_ptr(), label_faces.data_ptr(),
+          face_pixels.data_ptr(), C.byref(npx), C.byref(nfc), _STREAM)
+    return CaptureLabelled(materials, info, ret, st, count, label_faces, face_pixels, npx.value, nfc.value)
+
+
+class CaptureMaterials(NamedTuple):
+    """What fit_capture_materials returns: the materials' rows [label, channel], the face maps (CUDA tensors) and the host scalars."""
+    materials: object    # [K,3,3] float64
+    labels: object       # [nf] int32: the face's material; -1: no pixel carries the face, or no material could take it
+    face_sumsq: object   # [nf,3] float64: against the face's own material (+inf on a carried face with label -1)
+    face_count: object   # [nf,3] int32
+    info: object         # [K,3,10]: the last refit's; zeros if none ran
+    ret: object          # [K,3]: the last refit's; -1 if none ran
+    stats: FitStats | None
+    count: object        # [K,3] int32
+    label_faces: object  # [K] int32
+    face_pixels: object  # [nf] int32
+    rounds_used: int     # the refits
+    settled: bool        # the last assignment moved no label
+    changed: np.ndarray  # [assignments] int64: the faces whose label changed, per assignment
+    n_pixels: int
+    n_faces: int
+
+
+def fit_capture_materials(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, seeds, *, rounds: int = 20,
+                          v_min: int = 0, v_max: int = 255, cos_min: float = -2.0, rv_mode: int = 0, lb=(0.0, 0.0, 0.0), ub=(100.0, 100.0, 100.0),
+                          itmax: int = 100, opts=None, workspace_bytes: int = 0, want_stats: bool = True, validate: bool = True) -> CaptureMaterials:
+    """K materials and a label per face (brdf_hip_fit_capture_materials_dev): Lloyd's iteration with levmar as the centroid step.
+    seeds [K,3,3] (seed_materials gives a deterministic set; the caller's tensor is not written).  All labels start at -1; then
+    (1) assign every carried face to the material of least cost (s[f,k,0] + s[f,k,1]) + s[f,k,2] over capture_face_residuals' sums, a
+    cost that is not finite counting as +inf, the lowest k on a tie, the label staying where every cost is +inf -- assign_materials is
+    this step as NumPy code; (2) nothing changed: settled; `rounds` (0 ... 64) refits done: stop; (3) refit every material over its
+    faces from the current materials (fit_capture_labelled); after refit number `rounds` the loop ends without another assignment,
+    otherwise (1).  So `materials` are always fit_capture_labelled's bytes on `labels` from the materials of the round before;
+    rounds = 0 returns the seeds and one assignment.  face_sumsq / face_count come from one last residual pass."""
+    import torch
+    args, keep, nf = _capture_args(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, rv_mode, None, lb, ub, itmax, opts,
+                                   validate)
+    dev = keep[0].device
+    materials = _materials_tensor(seeds, dev, torch).clone()
+    K = int(materials.shape[0])
+    _require(0 <= int(rounds) <= 64, "rounds: 0 ... 64")
+    labels = torch.full((nf,), -1, dtype=torch.int32, device=dev)
+    face_sumsq = torch.zeros((nf, 3), dtype=torch.float64, device=dev)
+    face_count = torch.zeros((nf, 3), dtype=torch.int32, device=dev)
+    info, ret, st, count, label_faces, face_pixels = _labelled_maps(K, nf, dev, want_stats, torch)
+    used, settled = C.c_int(0), C.c_int(0)
+    changed = np.full(int(rounds) + 1, -1, dtype=np.int64)
+    npx, nfc = C.c_longlong(0), C.c_longlong(0)
+    _call("brdf_hip_fit_capture_materials_dev", dev, *args[:13], *args[14:18], int(v_min), int(v_max), float(cos_min), int(workspace_bytes), K,
+          int(rounds), materials.data_ptr(), labels.data_ptr(), face_sumsq.data_ptr(), face_count.data_ptr(), info.data_ptr(), ret.data_ptr(),
+          None if st is None else st.covar.data_ptr(), None if st is None else st.stats.data_ptr(), None if st is None else st.rank.data_ptr(),
+          count.data_ptr(), label_faces.data_ptr(), face_pixels.data_ptr(), C.byref(used), C.byref(settled),
+          changed.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(npx), C.byref(nfc), _STREAM)
+    return CaptureMaterials(materials, labels, face_sumsq, face_count, info, ret, st, count, label_faces, face_pixels, used.value, bool(settled.value),
+                            changed[changed >= 0], npx.value, nfc.value)
+
+
+class LabelSamples(NamedTuple):
+    """What group_capture_label_samples returns (NumPy): the packed batch fit_capture_labelled fits, rows channel * K + label."""
+    angles: np.ndarray       # [3 * total] float64
+    x: np.ndarray            # [total] float64
+    offsets: np.ndarray      # [3 K + 1] int64
+    label_faces: np.ndarray  # [K] int32: the carried faces of the label
+    face_pixels: np.ndarray  # [nf] int32
+
+
+def group_capture_label_samples(images, pixel_map, face_angles, model: int, labels, K: int, *, v_min: int = 0, v_max: int = 255,
+                                cos_min: float = -2.0) -> LabelSamples:
+    """The host twin of fit_capture_labelled's sample sets (NumPy, no device): its definition as code.  Arguments, candidates and
+    validity rule as group_capture_samples; labels [nf].  Fit (k, c) -- row c * K + k of the packed batch -- is the concatenation, over
+    the carried faces with label k in ascending order, of the sample sets group_capture_samples gives for (face, c).  A face whose
+    label is outside [0, K) takes part in nothing."""
+    a, x, off, fit_face, _, face_pixels = group_capture_samples(images, pixel_map, face_angles, model, v_min=v_min, v_max=v_max, cos_min=cos_min)
+    labels = np.asarray(labels).astype(np.int64)
+    _require(labels.shape == (face_pixels.size,) and K >= 1, "labels [nf], K >= 1")
+    carried = fit_face[0::3].astype(np.int64)  # (fits: ascending face, then channel)
+    label_faces = np.zeros(K, dtype=np.int32)
+    planes, xs, offsets = [], [], [0]
+    for c in range(3):
+        for k in range(K):
+            rows = np.flatnonzero(labels[carried] == k)
+            if c == 0:
+                label_faces[k] = rows.size
+            fit_planes, n = [np.zeros((3, 0))], 0
+            for r in rows:
+                s = 3 * int(r) + c
+                ks = int(off[s + 1] - off[s])
+                fit_planes.append(a[3 * off[s]:3 * off[s + 1]].reshape(3, ks))
+                xs.append(x[off[s]:off[s + 1]])
+                n += ks
+            planes.append(np.concatenate(fit_planes, axis=1).reshape(-1))
+            offsets.append(offsets[-1] + n)
+    cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0)  # noqa: E731
+    return LabelSamples(np.ascontiguousarray(cat(planes), dtype=np.float64), np.ascontiguousarray(cat(xs), dtype=np.float64),
+                        np.array(offsets, dtype=np.int64), label_faces, face_pixels)
+
+
+def assign_materials(face_sumsq, labels, carried=None):
+    """ONE assignment of fit_capture_materials as NumPy code.  face_sumsq [nf,K,3] (capture_face_residuals'), labels [nf] the current
+    labels, carried [nf] bool (optional): the faces a pixel carries -- the others are never assigned.  cost[f, k] =
+    (s[f,k,0] + s[f,k,1]) + s[f,k,2], in that order; a cost that is not finite is +inf; the new label is the least cost, the lowest k on
+    a tie; every cost +inf: the label stays.  Returns (new labels [nf] int32, the number of faces whose label changed)."""
+    s = np.asarray(face_sumsq, dtype=np.float64)
+    labels = np.asarray(labels).astype(np.int32)
+    _require(s.ndim == 3 and s.shape[2] == 3 and s.shape[1] >= 1 and labels.shape == (s.shape[0],), "face_sumsq [nf,K,3], labels [nf]")
+    with np.errstate(all="ignore"):
+        cost = (s[:, :, 0] + s[:, :, 1]) + s[:, :, 2]
+    cost = np.where(np.isfinite(cost), cost, np.inf)
+    best = np.argmin(cost, axis=1).astype(np.int32)  # (the first of equal costs)
+    takes = np.isfinite(cost[np.arange(cost.shape[0]), best])
+    if carried is not None:
+        takes &= np.asarray(carried, dtype=bool)
+    new = np.where(takes, best, labels).astype(np.int32)
+    return new, int((new != labels).sum())
+
+
+def seed_materials(K: int, model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, *, face_fits=None, min_count: int = 16,
+                   **capture):
+    """K deterministic seeds for fit_capture_materials, [K,3,3] NumPy.  Seed 0 is fit_capture_single_faces' result.  Seed j is the
+    per-face fit (`face_fits`: a fit_capture_faces result; computed here if None) of the face with the largest per-sample residual
+    against its nearest current seed -- the least of its costs (assign_materials') over capture_face_residuals' sums against seeds
+    0 ... j-1, divided by its samples of all three channels.  Only faces whose three fits have ret >= 0 and at least `min_count`
+    samples are eligible, and a face gives one seed at most; the lowest face index wins a tie.  **capture: the captures' keyword arguments (rule, rv_mode, p0, lb, ub,
+    itmax, opts, validate), passed on."""
+    _require(K >= 1, "K >= 1")
+    rule = {k: capture[k] for k in ("v_min", "v_max", "cos_min", "rv_mode", "validate") if k in capture}
+    single = fit_capture_single_faces(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, want_stats=False, **capture)
+    seeds = [np.array(single.single_brdf, dtype=np.float64)]
+    if K == 1:
+        return np.stack(seeds)
+    if face_fits is None:
+        face_fits = fit_capture_faces(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, want_stats=False, **capture)
+    surfaces, ret, count = (t.cpu().numpy() for t in (face_fits.surfaces, face_fits.ret, face_fits.count))
+    eligible = (ret >= 0).all(axis=1) & (count >= min_count).all(axis=1) & (face_fits.face_pixels.cpu().numpy() > 0)
+    _require(bool(eligible.any()), "no face has three fits with ret >= 0 and min_count samples")
+    samples = np.maximum(count.sum(axis=1), 1).astype(np.float64)
+    for _ in range(1, K):
+        res = capture_face_residuals(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, np.stack(seeds), **rule)
+        s = res.face_sumsq.cpu().numpy()
+        with np.errstate(all="ignore"):
+            cost = (s[:, :, 0] + s[:, :, 1]) + s[:, :, 2]
+        nearest = np.where(np.isfinite(cost), cost, np.inf).min(axis=1) / samples
+        nearest = np.where(eligible & np.isfinite(nearest), nearest, -np.inf)
+        f = int(np.argmax(nearest))  # (the first of equal values)
+        _require(bool(eligible[f]), "fewer eligible faces than seeds")
+        eligible[f] = False
+        seeds.append(np.array(surfaces[f], dtype=np.float64))
+    return np.stack(seeds)
+
+
 def host_dlevmar(method: int, model: int, angles: np.ndarray, x: np.ndarray, p0, *, lb=None, ub=None, dscl=None,
                  itmax=100, opts=None, want_covar=False) -> FitResult:
     """The drop-in call exactly as brdfdata.cpp:1058/1119 makes it: HOST arrays, a BRDFFunc-style callback

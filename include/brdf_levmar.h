@@ -733,6 +733,88 @@ int brdf_hip_fit_capture_single_faces_dev(int model, const unsigned char *d_imag
                                           double *covar, double *stats, int *rank, long long *count, double *d_face_sumsq, int *d_face_count,
                                           int *d_face_pixels, long long *n_pixels, long long *n_faces, void *stream);
 
+/* ---- K materials per object ------------------------------------------------------------------------------------------------------
+ * Between one fit per face (brdf_hip_fit_capture_faces_dev) and one per object (brdf_hip_fit_capture_single_faces_dev): a handful of
+ * materials and a label per face, by Lloyd's iteration with levmar as the centroid step.  Three entries: the carried faces' residuals
+ * against M candidate materials, one fit per (label, channel), and the loop around the two.  No fit or statistics kernel of their own:
+ * the fits are ONE packed batch.  Capture, mesh, leds, view_origin, rv_mode and the validity rule as
+ * brdf_hip_fit_capture_single_faces_dev; a material is [3][3]: channel (B, G, R), then {kd, ks, n}.
+ *
+ * brdf_hip_capture_face_residuals_dev: d_materials[M][3][3] (DEVICE) -> d_face_sumsq[nf][M][3], d_face_count[nf][3] (DEVICE, each may
+ * be NULL).
+ *   Value          for carried face f, material m, channel c: the sum over the face's valid samples of channel c of
+ *                  (x_i - f(materials[m][c]; sample i))^2, the model on the exact path.  The summation is the one
+ *                  brdf_hip_fit_capture_single_faces_dev uses for d_face_sumsq -- chunks of 1024 counted from the face's own first
+ *                  sample, lane l of a wavefront adds samples l, l + 64, ... in that order, one fixed tree over the lanes, the chunks'
+ *                  sums added in ascending order -- so column m has the BYTES that entry writes when its single_brdf equals
+ *                  materials[m], whatever M is and wherever m stands.  A sum that is not finite is stored as it comes.  No float
+ *                  atomics; two calls give the same bytes.  A carried face whose samples the rule removed gets 0.0 and 0; faces no
+ *                  pixel carries are left untouched in both maps.  d_face_pixels[nf] (DEVICE, may be NULL) is written for EVERY face.
+ *   Memory         32 bytes per valid sample, 24 bytes per carried pixel and the sort's scratch for the grouping, 8 M bytes per
+ *                  residual chunk (at most K_c / 1024 + carried faces chunks per channel).
+ *   Refused before any HIP call, under the entry's name: a NULL required pointer (images, map, mesh, leds, view origin, materials),
+ *                  M < 1, 3 M > INT_MAX, L outside [1, 64], H, W or nf <= 0, 3 nf > INT_MAX, an unknown model, v_min > v_max, a NaN
+ *                  cos_min.
+ *
+ * brdf_hip_fit_capture_labelled_dev: d_face_label[nf] (DEVICE int) and K; d_materials[K][3][3] (DEVICE) holds the starting points and
+ * receives the results, as brdf_hip_fit_batch_packed_dev's p.  A face whose label is outside [0, K) takes part in nothing.
+ *   Samples        of fit (k, c): the carried faces with label k in ascending face index, within a face its pixels in the reference's
+ *                  walk, within a pixel the lights 0 ... L-1, those the rule leaves for channel c.
+ *   Fit            the S = 3 K fits are rows c * K + k of one packed batch: materials[k][c], info[k][c], ret[k][c] have the BYTES
+ *                  brdf_hip_fit_batch_packed_dev (BRDF_METHOD_BC_DIF, lb, ub, itmax, opts, workspace_bytes) returns for that batch from
+ *                  the same starting points, covar / stats / rank those of brdf_hip_fit_stats_batch_packed_dev at the fitted points.
+ *                  Fewer than 3 samples is the packed call's refusal: ret LM_ERROR, zero info, the material untouched, rank 0.
+ *   Outputs        d_info[K][3][10], d_ret[K][3], d_covar[K][3][9], d_stats[K][3][BRDF_STATS_SZ], d_rank[K][3], d_count[K][3] (the
+ *                  fit's samples), d_label_faces[K] (the carried faces of the label): DEVICE, each may be NULL.
+ *   Memory         32 bytes per valid sample of a labelled face, 24 bytes per carried face and channel, 24 bytes per carried pixel and
+ *                  the sorts' scratch, the packed calls' workspace_bytes (0: 1 GiB).  The samples are placed from the candidates: no
+ *                  face-major copy of them is held.
+ *   Refused before any HIP call, under the entry's name: a NULL required pointer (images, map, mesh, leds, view origin, face_label,
+ *                  materials), K < 1, 3 K > INT_MAX, workspace_bytes < 0, L outside [1, 64], H, W or nf <= 0, 3 nf > INT_MAX, an
+ *                  unknown model, v_min > v_max, a NaN cos_min, lb > ub.
+ *   Empty capture  no carried face: every fit is refused (ret LM_ERROR, zeros in the other maps), the materials stay.
+ *
+ * brdf_hip_fit_capture_materials_dev: d_materials[K][3][3] holds the K seeds on entry; rounds in [0, 64].  All labels start at -1; then
+ *   1 assign       the residuals of every carried face against the K current materials (the first entry's kernels);
+ *                  cost[f][k] = (s[f][k][0] + s[f][k][1]) + s[f][k][2], a cost that is not finite is +inf; the new label is the least
+ *                  cost, the lowest k on a tie; every cost +inf: the label stays.  The faces whose label changed are counted.
+ *   2 settle/stop  nothing changed: settled.  `rounds` refits done: stop.
+ *   3 refit        the second entry's fit on the new labels from the current materials (a refused fit keeps its material); when this
+ *                  was refit number `rounds` the loop ends WITHOUT another assignment, otherwise go to 1.
+ * So the returned materials are always the labelled fit's bytes on the returned labels from the materials of the round before;
+ * rounds = 0 returns the seeds and one assignment.  One last residual pass against the returned materials fills the face maps.
+ *   Outputs        d_face_label[nf] (DEVICE, required): the labels, -1 on faces no pixel carries or no material could take;
+ *                  d_face_sumsq[nf][3] (may be NULL): the carried face's residual against its own material, +inf where its label is
+ *                  -1; d_face_count[nf][3] (may be NULL); both untouched on faces no pixel carries.  The second entry's maps of the
+ *                  last refit (ret LM_ERROR and zeros where none ran).  Host, each may be NULL: rounds_used (the refits), settled
+ *                  (0 / 1), changed[rounds + 1] (the changed faces per assignment, -1 behind the last).
+ *   Memory         that of the first entry with M = K plus that of the second: 64 bytes per valid sample -- one face-major copy for
+ *                  the residuals, one label-major copy for the fits -- 24 bytes per carried pixel, 24 K bytes per carried face for
+ *                  the cost table, 8 K bytes per residual chunk, the packed calls' workspace_bytes.
+ *   Waits          per round one for the changed count and the packed call's own.
+ *   Refused before any HIP call, under the entry's name: what the second entry refuses, and rounds outside [0, 64].
+ * All three synchronise `stream` before returning and return 0, or LM_ERROR for bad arguments or a HIP failure with a message that
+ * names the entry in brdf_hip_last_error().  Not covered: rounds over per-(face, light) means (they need weights above 16 samples),
+ * clipping inside the loop, a multi-GPU variant, choosing K, seeds (the Python package has a seeding rule; C callers bring their own). */
+int brdf_hip_capture_face_residuals_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                        const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                        const double *view_origin, int rv_mode, int v_min, int v_max, double cos_min, const double *d_materials, int M,
+                                        double *d_face_sumsq, int *d_face_count, int *d_face_pixels, long long *n_pixels, long long *n_faces,
+                                        void *stream);
+int brdf_hip_fit_capture_labelled_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                      const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                      const double *view_origin, int rv_mode, const double *lb, const double *ub, int itmax, const double *opts, int v_min,
+                                      int v_max, double cos_min, long long workspace_bytes, const int *d_face_label, int K, double *d_materials,
+                                      double *d_info, int *d_ret, double *d_covar, double *d_stats, int *d_rank, int *d_count, int *d_label_faces,
+                                      int *d_face_pixels, long long *n_pixels, long long *n_faces, void *stream);
+int brdf_hip_fit_capture_materials_dev(int model, const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                       const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                       const double *view_origin, int rv_mode, const double *lb, const double *ub, int itmax, const double *opts, int v_min,
+                                       int v_max, double cos_min, long long workspace_bytes, int K, int rounds, double *d_materials, int *d_face_label,
+                                       double *d_face_sumsq, int *d_face_count, double *d_info, int *d_ret, double *d_covar, double *d_stats, int *d_rank,
+                                       int *d_count, int *d_label_faces, int *d_face_pixels, int *rounds_used, int *settled, long long *changed,
+                                       long long *n_pixels, long long *n_faces, void *stream);
+
 /* ---- diagnostics ----------------------------------------------------------------------------------- */
 int brdf_hip_device_count(void);
 const char *brdf_hip_last_error(void);
