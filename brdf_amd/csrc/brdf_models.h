@@ -58,6 +58,18 @@ struct Prep {
 template <int MODEL>
 struct BrdfModel;
 
+// Column 2 of an analytic Jacobian row is (lobe factor s) x (a second factor: log c for Phong / Blinn-Phong, t2/a2 - 1 for Ward).
+// Where the lobe is dead -- s == 0 exactly: pow(0, n) with n > 0, or Ward's exp at cos(N.H) = 0 (tan^2 = inf) -- the second factor
+// is -inf / +inf, the product 0 * inf = NaN, and one such sample (a valid one: the reference evaluates pow(0, n) = 0 and fits on)
+// stopped dlevmar_bc_der / dlevmar_der with reason 5 at p0.  The derivative there is 0 (s vanishes faster than any power of
+// the factor grows), so the factor is replaced by its sign (`limit`) and the term becomes (+-0) * (+-1) = 0.  Only a
+// non-finite factor is replaced: a row that was finite keeps its bytes (a finite factor times s == 0 is the same signed
+// zero as before), and a NaN parameter or cosine still reaches the row through s or the factor's partner.  Phong's and
+// Blinn-Phong's prepared-sample path needs no select: its fit is kept only where domain_ok() holds, c > 0, and log c is finite.
+LM_HD double dead_lobe_factor(double s, double factor, double limit) {
+  return (s == 0.0 && !__builtin_isfinite(factor)) ? limit : factor;
+}
+
 // Phong: x = p0*c0 + ((p2+2)/2*PI)*p1*pow(c2,p2)          brdfdata.cpp:981 (note: *PI, not /(2PI))
 template <>
 struct BrdfModel<MODEL_PHONG> {
@@ -72,14 +84,15 @@ struct BrdfModel<MODEL_PHONG> {
   static LM_HD double shape(const Nl &u, double, const Prep &q) { return FAST ? exp(u.u0 * q.q1) : pow(q.q1, u.u0); }
   static LM_HD double combine(const Lin &l, double c0, double s) { return l.a * c0 + l.b * s; }
   // analytic Jacobian row (not in the reference): with A = (p2+2)/2*PI, s = pow(c2, p2):
-  //   df/dp0 = c0,  df/dp1 = A s,  df/dp2 = (1/2*PI p1) s + ((A p1) s) log c2
+  //   df/dp0 = c0,  df/dp1 = A s,  df/dp2 = (1/2*PI p1) s + ((A p1) s) log c2        (log c2 -> -1 where s == 0 and log c2 is
+  //   not finite: dead_lobe_factor above.  Every entry is held to a 50-digit derivative: tests/jacobian_yardstick.py)
   static LM_HD void an_scalars(const double *p, double *an) {
     an[0] = (p[2] + 2.0) / 2.0 * kPi;
     an[1] = (1.0 / 2.0 * kPi) * p[1];
   }
   template <bool FAST>
   static LM_HD void an_row(const double *an, const Lin &l, const Nl &, double c0, const Prep &q, double s, double *j) {
-    const double lc = FAST ? q.q1 : log(q.q1);
+    const double lc = FAST ? q.q1 : dead_lobe_factor(s, log(q.q1), -1.0);  // (FAST: kept only where domain_ok() holds: log c is finite)
     j[0] = c0;
     j[1] = an[0] * s;
     j[2] = an[1] * s + (l.b * s) * lc;
@@ -99,14 +112,14 @@ struct BrdfModel<MODEL_BLINN_PHONG> {
   template <bool FAST>
   static LM_HD double shape(const Nl &u, double, const Prep &q) { return FAST ? exp(u.u0 * q.q1) : pow(q.q1, u.u0); }
   static LM_HD double combine(const Lin &l, double c0, double s) { return l.a * c0 + l.b * s; }
-  // analytic Jacobian row: s = pow(c1, p2):  df/dp0 = c0,  df/dp1 = s,  df/dp2 = (p1 s) log c1
+  // analytic Jacobian row: s = pow(c1, p2):  df/dp0 = c0,  df/dp1 = s,  df/dp2 = (p1 s) log c1     (dead lobe: as Phong's)
   static LM_HD void an_scalars(const double *p, double *an) {
     an[0] = p[1];
     an[1] = 0.0;
   }
   template <bool FAST>
   static LM_HD void an_row(const double *an, const Lin &, const Nl &, double c0, const Prep &q, double s, double *j) {
-    const double lc = FAST ? q.q1 : log(q.q1);
+    const double lc = FAST ? q.q1 : dead_lobe_factor(s, log(q.q1), -1.0);  // (FAST: kept only where domain_ok() holds: log c is finite)
     j[0] = c0;
     j[1] = s;
     j[2] = (an[0] * s) * lc;
@@ -169,6 +182,7 @@ struct BrdfModel<MODEL_WARD> {
   static LM_HD double combine(const Lin &l, double c0, double s) { return c0 * (l.a + l.b * s); }
   // analytic Jacobian row: with S = (k g) rinv (what shape() returns), k = 1/(4 PI a2), g = exp(-t2/a2), a2 = p2^2:
   //   df/dp0 = c0/PI,  df/dp1 = c0 S,  df/dp2 = c0 ((p1 S) ((2/p2) (t2/a2 - 1)))        (dk/dp2 = -2k/p2, dg/dp2 = g t2 2/p2^3)
+  //   (t2/a2 - 1 -> 1 where S == 0 and t2/a2 is infinite, cos(N.H) at or below ~1e-154: dead_lobe_factor above)
   static LM_HD void an_scalars(const double *p, double *an) {
     an[0] = p[1];
     an[1] = 2.0 / p[2];
@@ -178,7 +192,7 @@ struct BrdfModel<MODEL_WARD> {
     const double t2 = FAST ? q.q1 : ward_invariants(c0, q.q1, q.q2).q1;
     j[0] = c0 / kPi;
     j[1] = c0 * s;
-    j[2] = c0 * ((an[0] * s) * (an[1] * (t2 * u.u0 - 1.0)));
+    j[2] = c0 * ((an[0] * s) * (an[1] * dead_lobe_factor(s, t2 * u.u0 - 1.0, 1.0)));
   }
 };
 

@@ -57,7 +57,18 @@ void orc_brdf_func(double *p, double *hx, int m, int n, void *adata)
 
 /* Analytic Jacobian of the three models, n x 3 row-major like every levmar jacf (NOT in
  * the reference, which only ever differentiates numerically; checked with the reference's own dlevmar_chkjac in
- * tests/test_oracle_brdf.py).  Same sub-expressions, same order as orc_brdf_func. */
+ * tests/test_oracle_brdf.py, and entry by entry against 50-digit derivatives in tests/test_oracle_jacobian.py).  Same
+ * sub-expressions, same order as orc_brdf_func.
+ *
+ * dead_lobe_factor: column 2 is (lobe factor s) x (log c, or Ward's t2/a2 - 1).  Where s == 0 exactly and that factor is not finite
+ * (pow(0, n), n > 0: log 0 = -inf; Ward at cos(N.H) <~ 1e-154: t2/a2 = inf) the product was 0 * inf = NaN although the derivative
+ * is 0; the factor is replaced by its sign, the term becomes a zero.  A finite factor is left alone, so every row that was finite
+ * keeps its bytes.  The product's brdf_models.h does the same, operation for operation. */
+static double dead_lobe_factor(double s, double factor, double limit)
+{
+  return (s == 0.0 && !isfinite(factor)) ? limit : factor;
+}
+
 void orc_brdf_jac(double *p, double *jac, int m, int n, void *adata)
 {
   const struct orc_extra_data *d = (const struct orc_extra_data *)adata;
@@ -68,7 +79,7 @@ void orc_brdf_jac(double *p, double *jac, int m, int n, void *adata)
   case 0: {
     const double A = (p[2] + 2.0) / 2.0 * ORC_PI, dA = (1.0 / 2.0 * ORC_PI) * p[1], b = A * p[1];
     for (i = 0; i < n; ++i) {
-      const double s = pow(c_p2[i], p[2]), lc = log(c_p2[i]);
+      const double s = pow(c_p2[i], p[2]), lc = dead_lobe_factor(s, log(c_p2[i]), -1.0);
       jac[3 * i] = c_ln[i];
       jac[3 * i + 1] = A * s;
       jac[3 * i + 2] = dA * s + (b * s) * lc;
@@ -77,7 +88,7 @@ void orc_brdf_jac(double *p, double *jac, int m, int n, void *adata)
   }
   case 1:
     for (i = 0; i < n; ++i) {
-      const double s = pow(c_nh[i], p[2]), lc = log(c_nh[i]);
+      const double s = pow(c_nh[i], p[2]), lc = dead_lobe_factor(s, log(c_nh[i]), -1.0);
       jac[3 * i] = c_ln[i];
       jac[3 * i + 1] = s;
       jac[3 * i + 2] = (p[1] * s) * lc;
@@ -94,7 +105,7 @@ void orc_brdf_jac(double *p, double *jac, int m, int n, void *adata)
       const double spec = (k * g) * rinv;
       jac[3 * i] = ci / ORC_PI;
       jac[3 * i + 1] = ci * spec;
-      jac[3 * i + 2] = ci * ((p[1] * spec) * (two_over * (t2 * ia2 - 1.0)));
+      jac[3 * i + 2] = ci * ((p[1] * spec) * (two_over * dead_lobe_factor(spec, t2 * ia2 - 1.0, 1.0)));
     }
     break;
   }

@@ -98,6 +98,45 @@ def make(family: str, model: int, n: int, index: int = 0):
     return (np.ascontiguousarray(angles), np.ascontiguousarray(x, dtype=np.float64), p0, lb, ub)
 
 
+# ---- dead lobes: samples whose lobe factor is exactly 0, where the analytic Jacobian's third column was 0 * inf ----------------
+# Kept apart from FAMILIES: its fits are pinned by tests/golden/brdf_dead_lobe_fits.json (the reference's finite-difference
+# optimum), not by brdf_edge_fits.json.
+WARD_DEAD_COSINES = (0.0, 5e-320, 1e-200)  # cos(N.H): tan^2 = inf outright / c1^2 underflows to 0 / tan^2 = 1e400 overflows
+DEAD_LOBE_N = (16, 64, 256, 1000, 1024, 4096, 4097, 5000)  # the CPU tests' sizes and one per device regime and batched kernel
+
+
+def make_ward_dead_lobe(n: int, index: int = 0):
+    """Ward on the planes of the `quantised` family with cos(N.H) at 1::max(2, n // 4) set to 0, 5e-320 and 1e-200 in turn
+    (index rotates the turn); x is the truth's value plus make()'s noise.  Every cosine is valid: the model value there is
+    the diffuse term alone."""
+    angles, _, p0, lb, ub = make("quantised", 2, n, index)
+    where = np.arange(1, n, max(2, n // 4))
+    angles[1, where] = [WARD_DEAD_COSINES[(i + index) % 3] for i in range(where.size)]
+    with np.errstate(divide="ignore", over="ignore"):
+        x = synth.model_value(2, truth(2), angles[0], angles[1], angles[2])
+    x = x + 0.01 * (_u("quantised", 2, n, index, 3) - 0.5)
+    assert np.all(np.isfinite(x))
+    return (np.ascontiguousarray(angles), np.ascontiguousarray(x, dtype=np.float64), p0, lb, ub)
+
+
+def make_dead_lobe(model: int, n: int, index: int = 0):
+    """a problem with dead-lobe samples and no invalid one: `nonpositive` index 0 / 1 (zeros, no negative cosine) for Phong and
+    Blinn-Phong, make_ward_dead_lobe for Ward"""
+    assert index in (0, 1)
+    return make("nonpositive", model, n, index) if model in (0, 1) else make_ward_dead_lobe(n, index)
+
+
+def dead_lobe_args(model: int, n: int, index: int = 0):
+    """fit_args() of a dead-lobe problem"""
+    angles, x, p0, lb, ub = make_dead_lobe(model, n, index)
+    return angles, x, p0, synth.ITMAX, synth.OPTS, lb, ub
+
+
+def dead_lobe_cases():
+    """(model, n, index) of tests/golden/brdf_dead_lobe_fits.json, in its order (each with the box and without)"""
+    return [(model, n, idx) for model in (0, 1, 2) for n in DEAD_LOBE_N for idx in (0, 1)]
+
+
 def cases(models=(0, 1, 2), families=None):
     """(family, model) pairs in a fixed order"""
     fams = FAMILIES if families is None else families

@@ -15,6 +15,10 @@
   brdf_edge_fits.json the reference's fits on the edge-of-domain families of tests/edge_problems.py (active bounds, black and
                    saturated pixels, grazing and non-positive cosines, starts on the box): one compact row per fit,
                    [family, model, method, n, index, ret, p[3], info[10]] (inputs regenerated from the family's seed).
+  brdf_dead_lobe_fits.json the reference's dlevmar_bc_dif / dlevmar_dif on the dead-lobe problems of tests/edge_problems.py
+                   (make_dead_lobe): the finite-difference optimum, which owes nothing to this project's analytic Jacobian and
+                   which dlevmar_bc_der / dlevmar_der on the same data are held to.  One row per fit,
+                   [model, method (1 / 0), n, index, ret, p[3], info[10]].
 """
 import ctypes as C
 import json
@@ -56,6 +60,15 @@ def main():
         fh.write(",\n".join(json.dumps(row, separators=(",", ":")) for row in edge))
         fh.write("\n]}\n")
 
+    dead = [[model, method, n, idx, int(r), [float.hex(v) for v in p], [float.hex(v) for v in info]]
+            for model, n, idx in E.dead_lobe_cases() for method in (1, 0)
+            for r, p, info in [L.brdf_fit("ref", method, model, *E.dead_lobe_args(model, n, idx))]]
+    with open(os.path.join(HERE, "brdf_dead_lobe_fits.json"), "w") as fh:
+        fh.write('{"generator": "tests.edge_problems.make_dead_lobe(model, n, index)", "itmax": %d, "opts": %s, "fits": [\n'
+                 % (synth.ITMAX, json.dumps([float.hex(v) for v in synth.OPTS])))
+        fh.write(",\n".join(json.dumps(row, separators=(",", ":")) for row in dead))
+        fh.write("\n]}\n")
+
     kats = []
     for pid, pr in PROBLEMS.items():
         r, p, info, covar = run_problem(L.ref, "", pr)
@@ -79,7 +92,7 @@ def main():
             vals.append({"model": model, "p": list(p), "source": "ref_BRDFFunc (brdfdata.cpp:962-989 compiled in place)" if model < 2
                          else "oracle/brdf_models_oracle.c (Ward is build-defined)", "hx": [float.hex(v) for v in hx]})
     json.dump({"n": 64, "values": vals}, open(os.path.join(HERE, "model_values.json"), "w"), indent=1)
-    print("wrote", len(fits), "fits,", len(edge), "edge fits,", len(kats), "kats,", len(vals), "model value sets")
+    print("wrote", len(fits), "fits,", len(edge), "edge fits,", len(dead), "dead-lobe fits,", len(kats), "kats,", len(vals), "model value sets")
 
 
 if __name__ == "__main__":
