@@ -151,17 +151,28 @@ constexpr int sample_fields() { return METHOD == 0 ? 7 : 4; }
 
 template <int METHOD>
 struct RegSamples {
-  static constexpr bool kUnrolled = true;
+  static constexpr bool kUnrolled = true, kFlips = false;
   double v[sample_fields<METHOD>()][kRSpt];
   __device__ __forceinline__ double get(int f, int k) const { return v[f][k]; }
   __device__ __forceinline__ void set(int f, int k, double x) { v[f][k] = x; }
 };
-template <int METHOD>
+// FLIPS (the control wave of a single dlevmar_dif fit; the batched kernels keep the plain form and their code): "hx <- wrk" on an
+// accepted step is a flip of which plane is which -- flip_hx(): a wave-uniform offset added to the two fields' addresses -- and
+// not eight ds_read / ds_write pairs in front of the sweep.  After a flip wrk holds the OLD f(p) instead of a second copy of the
+// new one: nothing reads wrk before the next trial sweep has written it, and every flip has a trial sweep behind it.
+template <int METHOD, bool FLIPS = false>
 struct LdsSamples {
-  static constexpr bool kUnrolled = false;
+  static constexpr bool kUnrolled = false, kFlips = FLIPS;
   double *base;  // + lane
-  __device__ __forceinline__ double get(int f, int k) const { return base[(f * kRSpt + k) * kWave]; }
-  __device__ __forceinline__ void set(int f, int k, double x) { base[(f * kRSpt + k) * kWave] = x; }
+  int hx_off;    // FLIPS: 0, or one field's stride while f(p) lives in the plane named kFwrk and f(p + Dp) in kFhx's
+  __device__ __forceinline__ int at(int f, int k) const {
+    const int i = (f * kRSpt + k) * kWave;
+    if constexpr (FLIPS) return i + (f == kFhx ? hx_off : f == kFwrk ? -hx_off : 0);
+    return i;
+  }
+  __device__ __forceinline__ double get(int f, int k) const { return base[at(f, k)]; }
+  __device__ __forceinline__ void set(int f, int k, double x) { base[at(f, k)] = x; }
+  __device__ __forceinline__ void flip_hx() { hx_off = (kFwrk - kFhx) * kRSpt * kWave - hx_off; }
 };
 
 template <bool UNROLLED, class F>

@@ -102,7 +102,7 @@ RESIDENT_KERNEL_HEAD {
   const int nk = (tile + kRThreads - 1) / kRThreads;  // occupied sample slots of a lane (workgroup-uniform)
   const int nfull = max(end - begin, 0) / kRThreads;   // slots in which every lane of this workgroup holds a sample
   RegSamples<METHOD> rs;
-  LdsSamples<METHOD> ls{cst + (tid & (kWave - 1))};
+  LdsSamples<METHOD, METHOD == 0 && !BATCHED> ls{cst + (tid & (kWave - 1)), 0};
   unsigned okm = 0;
   {
     bool bad = false;
@@ -153,8 +153,13 @@ RESIDENT_KERNEL_HEAD {
       pend = sm.h.req.sel_j != cur_sel_j;  // the Broyden update was adopted: J += tb Dp^T, applied by the next trial sweep
       if (pend && sm.h.req.kind != RQ_DIF_TRIAL) pend = false;  // (a fresh FD Jacobian overwrites J anyway)
       cur_sel_j = sm.h.req.sel_j;
-      if (sm.h.req.sel_hx != cur_sel_hx) {  // step accepted: hx <- f(p + Dp)
-        for_samples<std::remove_reference<decltype(st)>::type::kUnrolled>(nk, [&](int k) { st.set(kFhx, k, st.get(kFwrk, k)); });
+      using Store = typename std::remove_reference<decltype(st)>::type;
+      if constexpr (Store::kFlips) {  // step accepted: the two planes trade names (LdsSamples)
+        const int sel = lm_uniform(sm.h.req.sel_hx);
+        if (sel != cur_sel_hx) st.flip_hx();
+        cur_sel_hx = sel;
+      } else if (sm.h.req.sel_hx != cur_sel_hx) {  // step accepted: hx <- f(p + Dp)
+        for_samples<Store::kUnrolled>(nk, [&](int k) { st.set(kFhx, k, st.get(kFwrk, k)); });
         cur_sel_hx = sm.h.req.sel_hx;
       }
     }
