@@ -15,4 +15,6 @@ from .fit import (METHOD_BC_DER, METHOD_BC_DIF, METHOD_DER, METHOD_DIF, MODEL_BL
                   ClippedFit, CaptureFacesClipped, SIGMA_MIN_8BIT, fit_batch_packed_clipped, fit_capture_faces_clipped, clip_samples, last_clip_stats,
                   CaptureMeansClipped, fit_capture_means_clipped, clip_light_means, initial_light_intervals,
                   FaceResiduals, CaptureLabelled, CaptureMaterials, LabelSamples, capture_face_residuals, fit_capture_labelled, fit_capture_materials,
-                  group_capture_label_samples, assign_materials, seed_materials)
+                  group_capture_label_samples, assign_materials, seed_materials,
+                  CaptureRender, CaptureRenderResiduals, RenderResidualsHost, capture_render, capture_render_residuals, surfaces_from_materials,
+                  render_capture_host, render_residuals_host)

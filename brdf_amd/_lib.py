@@ -143,6 +143,13 @@ ABI = {
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, I, I, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
                                                      C.POINTER(C.c_longlong), C.c_void_p]),
+    "brdf_hip_capture_render_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, D, C.c_int, D,
+                                              C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "brdf_hip_capture_render_residuals_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_int, D, D, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
+    "brdf_hip_surfaces_from_materials_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, D, C.c_void_p, C.c_void_p]),
     "brdf_hip_device_count": (C.c_int, []),
     "brdf_hip_last_error": (C.c_char_p, []),
     "brdf_hip_last_fit_launches": (C.c_longlong, []),

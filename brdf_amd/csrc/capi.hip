@@ -927,6 +927,36 @@ int brdf_hip_fit_capture_materials_dev(int model, const unsigned char *d_images,
   return capture_materials_run(a);
 }
 
+// the rendering entries (capture_fit.h: capture_render.hip) fit nothing; their lights are the call's own
+int brdf_hip_capture_render_dev(int model, int H, int W, const int *d_pixel_map, const double *d_vertices, const int *d_faces,
+                                const double *d_face_normals, int nf, const double *leds, int Lr, const double *view_origin, int rv_mode,
+                                const double *d_brdf_surfaces, int background, double *d_face_values, unsigned char *d_rendered, void *stream) {
+  const unsigned char *d_images = nullptr;
+  const int L = Lr;
+  const CaptureRenderArgs a = {CAPTURE_ARGS_NO_START(nullptr, nullptr, 0, nullptr), d_brdf_surfaces, background, d_face_values, d_rendered};
+  return capture_render_run(a);
+}
+
+int brdf_hip_capture_render_residuals_dev(int model, const unsigned char *d_images, int Lr, int H, int W, const int *d_pixel_map,
+                                          const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                          const double *view_origin, int rv_mode, const double *d_brdf_surfaces, int v_min, int v_max,
+                                          double cos_min, long long *d_light_count, long long *d_light_sum, long long *d_light_sumsq,
+                                          int *d_face_light_count, long long *d_face_light_sum, long long *d_face_light_sumsq,
+                                          unsigned char *d_abs_max, unsigned char *d_worst_light, double *d_face_values, long long *n_pixels,
+                                          void *stream) {
+  const int L = Lr;
+  const CaptureRenderResidualsArgs a = {{CAPTURE_ARGS_NO_START(nullptr, nullptr, 0, nullptr), v_min, v_max, cos_min, nullptr, n_pixels, nullptr},
+                                        d_brdf_surfaces, d_light_count, d_light_sum, d_light_sumsq, d_face_light_count, d_face_light_sum,
+                                        d_face_light_sumsq, d_abs_max, d_worst_light, d_face_values};
+  return capture_render_residuals_run(a);
+}
+
+int brdf_hip_surfaces_from_materials_dev(const int *d_face_label, int nf, const double *d_materials, int K, const double *fill,
+                                         double *d_brdf_surfaces, void *stream) {
+  const SurfacesFromMaterialsArgs a = {d_face_label, nf, d_materials, K, fill, d_brdf_surfaces, static_cast<hipStream_t>(stream)};
+  return surfaces_from_materials_run(a);
+}
+
 #undef CAPTURE_ARGS_NO_START
 #undef CAPTURE_ARGS
 

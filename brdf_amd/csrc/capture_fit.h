@@ -152,4 +152,39 @@ struct CaptureMaterialsArgs {
   long long *changed;          // host [rounds + 1] or null: the faces whose label changed, per assignment (-1: no such assignment)
 };
 
+// brdf_hip_capture_render_dev (capture_render.hip): the model at the fitted surfaces under `L` lights of any kind, as a value table
+// and as 8-bit images in the captures' layout
+struct CaptureRenderArgs {
+  CaptureArgs cap;  // (d_images, p0, lb, ub, itmax, opts unused: no capture is read, no fit)
+  const double *d_brdf_surfaces;  // [nf][3][3], required
+  int background;                 // -1: pixels that carry no face are left untouched; otherwise their grey level
+  double *d_face_values;          // [nf][3][L] or null
+  unsigned char *d_rendered;      // [L][H][W][3] or null
+};
+int capture_render_run(const CaptureRenderArgs &a);  // refuses bad arguments before any HIP call
+
+// brdf_hip_capture_render_residuals_dev (capture_render.hip): the captures minus the rendered grey levels, as integer maps
+struct CaptureRenderResidualsArgs {
+  CaptureGrouped g;  // (p0, lb, ub, itmax, opts, d_face_pixels, n_faces unused)
+  const double *d_brdf_surfaces;  // [nf][3][3], required
+  long long *d_light_count, *d_light_sum, *d_light_sumsq;  // [L][3] or null
+  int *d_face_light_count;                                 // [nf][3][L] or null
+  long long *d_face_light_sum, *d_face_light_sumsq;        // [nf][3][L] or null
+  unsigned char *d_abs_max, *d_worst_light;                // [H][W][3] at map coordinates, or null
+  double *d_face_values;                                   // [nf][3][L] or null
+};
+int capture_render_residuals_run(const CaptureRenderResidualsArgs &a);  // refuses bad arguments before any HIP call
+
+// brdf_hip_surfaces_from_materials_dev (capture_render.hip): surfaces[f] = materials[label[f]], `fill` where the label is outside [0, K)
+struct SurfacesFromMaterialsArgs {
+  const int *d_face_label;  // [nf]
+  int nf;
+  const double *d_materials;  // [K][3][3]
+  int K;
+  const double *fill;       // host [3]
+  double *d_brdf_surfaces;  // [nf][3][3]
+  hipStream_t stream;
+};
+int surfaces_from_materials_run(const SurfacesFromMaterialsArgs &a);  // refuses bad arguments before any HIP call
+
 }  // namespace brdf

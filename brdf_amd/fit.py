@@ -1491,3 +1491,219 @@ def set_launch_timing(on: bool) -> None:
     """resident fits bracket their launch with a HIP event pair on the launch stream; last_fit_stats()["kernel_us"] /
     last_channels_stats()["kernel_us"] then hold the kernel's duration (-1 otherwise)"""
     lib.brdf_hip_set_launch_timing(1 if on else 0)
+
+
+# ---- rendering a fitted capture: predicted images, residual maps, held-out lights -----------------------------------------------------
+def _grey_levels(values: np.ndarray) -> np.ndarray:
+    """The grey level of a model value: t = 255.0 * v + 0.5; q = !(t >= 0) ? 0 : (t >= 256.0 ? 255 : (int)t).  A NaN gives 0."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = 255.0 * np.asarray(values, dtype=np.float64) + 0.5
+        q = np.zeros(t.shape, dtype=np.uint8)
+        inside = (t >= 0.0) & (t < 256.0)
+        q[inside] = t[inside].astype(np.int64)
+        q[t >= 256.0] = 255
+    return q
+
+
+def render_capture_host(face_values, pixel_map, background: int, out=None) -> np.ndarray:
+    """The host twin of capture_render's images (NumPy, no device): their definition as code.  face_values [nf,3,Lr] float64 (the
+    model per face, channel and light), pixel_map [H,W].  Returns uint8 [Lr,H,W,3]: map pixel (y, x) with a face in [0, nf) writes the
+    grey level of (face, c, l) to [l, H-1-y, x, c]; any other pixel receives `background` (0 ... 255), or with background = -1 keeps
+    what `out` held (zeros without one)."""
+    face_values, pixel_map = np.asarray(face_values, dtype=np.float64), np.asarray(pixel_map)
+    _require(face_values.ndim == 3 and face_values.shape[1] == 3 and pixel_map.ndim == 2, "face_values [nf,3,Lr], pixel_map [H,W]")
+    _require(-1 <= int(background) <= 255, "background: -1 or 0 ... 255")
+    nf, _, Lr = face_values.shape
+    H, W = pixel_map.shape
+    if out is None:
+        out = np.zeros((Lr, H, W, 3), dtype=np.uint8)
+    _require(out.shape == (Lr, H, W, 3) and out.dtype == np.uint8, "out: uint8 [Lr,H,W,3]")
+    grey = _grey_levels(face_values)  # [nf,3,Lr]
+    flipped = pixel_map[::-1]         # image row r is map row H - 1 - r
+    carried = (flipped > -1) & (flipped < nf)
+    if int(background) >= 0:
+        out[:, ~carried, :] = int(background)
+    out[:, carried, :] = grey[flipped[carried]].transpose(2, 0, 1)  # [pixels,3,Lr] -> [Lr,pixels,3]
+    return out
+
+
+class RenderResidualsHost(NamedTuple):
+    """What render_residuals_host returns (NumPy): capture_render_residuals' integer maps."""
+    light_count: np.ndarray       # [Lr,3] int64
+    light_sum: np.ndarray         # [Lr,3] int64
+    light_sumsq: np.ndarray       # [Lr,3] int64
+    face_light_count: np.ndarray  # [nf,3,Lr] int32
+    face_light_sum: np.ndarray    # [nf,3,Lr] int64
+    face_light_sumsq: np.ndarray  # [nf,3,Lr] int64
+    abs_max: np.ndarray           # [H,W,3] uint8
+    worst_light: np.ndarray       # [H,W,3] uint8
+
+
+def render_residuals_host(images, pixel_map, face_angles, model: int, face_values, *, v_min: int = 0, v_max: int = 255,
+                          cos_min: float = -2.0) -> RenderResidualsHost:
+    """The host twin of capture_render_residuals (NumPy, no device): its definition as code.  images [Lr,H,W,3] uint8, pixel_map [H,W],
+    face_angles [nf,3,Lr] (the faces' cosine planes under these lights), face_values [nf,3,Lr].  A candidate (carried pixel, light l,
+    channel c) is compared iff v_min <= image_l(H-1-y, x)[c] <= v_max and every plane the model reads is > cos_min (a NaN is not);
+    d = measured - grey level of (face, c, l).  Sums of 1, d, d^2 per (light, channel) and per (face, channel, light); per pixel, at
+    map coordinates, max |d| over the compared lights and the lowest light that attains it (0 and 255 where nothing is compared)."""
+    images, pixel_map = np.asarray(images), np.asarray(pixel_map)
+    face_angles, face_values = np.asarray(face_angles, dtype=np.float64), np.asarray(face_values, dtype=np.float64)
+    _require(images.ndim == 4 and images.shape[3] == 3 and images.dtype == np.uint8 and pixel_map.shape == images.shape[1:3],
+             "images [Lr,H,W,3] uint8, pixel_map [H,W]")
+    L, H, W = images.shape[:3]
+    _require(face_angles.ndim == 3 and face_angles.shape[1:] == (3, L) and face_values.shape == face_angles.shape,
+             "face_angles, face_values [nf,3,Lr]")
+    _require(model in (MODEL_PHONG, MODEL_BLINN_PHONG, MODEL_WARD), "unknown model")
+    nf = face_angles.shape[0]
+    ys, xs = np.nonzero((pixel_map > -1) & (pixel_map < nf))
+    face = pixel_map[ys, xs].astype(np.int64)
+    measured = images[:, H - 1 - ys, xs, :].astype(np.int64).transpose(1, 2, 0)  # [pixels,3,Lr]
+    reads = [True, model != MODEL_PHONG, model != MODEL_BLINN_PHONG]  # the planes the model reads
+    with np.errstate(invalid="ignore"):
+        cos_ok = np.all([face_angles[face, k, :] > cos_min for k in range(3) if reads[k]], axis=0)  # [pixels,Lr]
+    compared = cos_ok[:, None, :] & (measured >= v_min) & (measured <= v_max)
+    d = np.where(compared, measured - _grey_levels(face_values)[face].astype(np.int64), 0)
+    n = compared.astype(np.int64)
+    fl = [np.zeros((nf, 3, L), dtype=np.int64) for _ in range(3)]
+    for acc, term in zip(fl, (n, d, d * d)):
+        np.add.at(acc, face, term)
+    mag = np.where(compared, np.abs(d), -1)  # [pixels,3,Lr]
+    worst = np.argmax(mag, axis=2)           # the first (lowest) light of the maximum
+    top = np.take_along_axis(mag, worst[:, :, None], axis=2)[:, :, 0]
+    abs_max, worst_light = np.zeros((H, W, 3), dtype=np.uint8), np.full((H, W, 3), 255, dtype=np.uint8)
+    abs_max[ys, xs] = np.where(top >= 0, top, 0)
+    worst_light[ys, xs] = np.where(top >= 0, worst, 255)
+    return RenderResidualsHost(fl[0].sum(axis=0).T.copy(), fl[1].sum(axis=0).T.copy(), fl[2].sum(axis=0).T.copy(), fl[0].astype(np.int32), fl[1],
+                               fl[2], abs_max, worst_light)
+
+
+def _psnr(count, sumsq):
+    """10 log10(255^2 count / sumsq): inf at sumsq = 0, NaN at count = 0"""
+    count, sumsq = np.asarray(count, dtype=np.float64), np.asarray(sumsq, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = 10.0 * np.log10(65025.0 * count / sumsq)
+    out = np.where(sumsq == 0, np.inf, out)
+    return np.where(count == 0, np.nan, out)
+
+
+class CaptureRender(NamedTuple):
+    """What capture_render returns (CUDA tensors)."""
+    face_values: object  # [nf,3,Lr] float64: the model per face, channel and light; None where not asked for
+    rendered: object     # [Lr,H,W,3] uint8 BGR, the captures' layout; None where not asked for
+
+
+def _render_args(model, pixel_map, vertices, faces, face_normals, leds, view_origin, surfaces, validate):
+    import torch
+    pixel_map, vertices, faces, face_normals = pixel_map.contiguous(), vertices.contiguous(), faces.contiguous(), face_normals.contiguous()
+    _require(pixel_map.is_cuda and vertices.is_cuda and faces.is_cuda and face_normals.is_cuda, "pixel_map, vertices, faces, face_normals: CUDA tensors")
+    _require(pixel_map.dtype == torch.int32 and pixel_map.dim() == 2 and faces.dtype == torch.int32, "pixel_map int32 [H,W], faces int32")
+    _require(vertices.dtype == torch.float64 and face_normals.dtype == torch.float64, "vertices, face_normals: float64")
+    _require(tuple(face_normals.shape) == (faces.shape[0], 3) and vertices.shape[-1] == 3 and faces.shape[-1] == 3, "faces, face_normals [nf,3], vertices [nv,3]")
+    if validate:
+        _check_indices(faces, vertices.shape[0], "face index outside the vertex array")
+    nf, dev = int(faces.shape[0]), pixel_map.device
+    la = np.ascontiguousarray(leds, dtype=np.float64).reshape(-1, 3)
+    if not torch.is_tensor(surfaces):
+        surfaces = torch.from_numpy(np.ascontiguousarray(surfaces, dtype=np.float64)).to(dev)
+    surfaces = surfaces.contiguous()
+    _require(surfaces.is_cuda and surfaces.device == dev and surfaces.dtype == torch.float64 and tuple(surfaces.shape) == (nf, 3, 3),
+             "surfaces: [nf,3,3] float64 on the map's device")
+    return pixel_map, vertices, faces, face_normals, la, _f64(view_origin, 3), surfaces, nf, dev
+
+
+def _out_tensor(t, shape, dtype, dev, what, torch, fill=0):
+    if t is None:
+        return torch.full(shape, fill, dtype=dtype, device=dev)
+    _require(torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous(),
+             f"{what}: contiguous CUDA {dtype} {list(shape)} on the capture's device")
+    return t
+
+
+def capture_render(model: int, pixel_map, vertices, faces, face_normals, leds, view_origin, surfaces, *, background: int = 0, rv_mode: int = 0,
+                   want_values: bool = True, want_images: bool = True, rendered=None, validate: bool = True) -> CaptureRender:
+    """Shade the mesh with fitted parameters (brdf_hip_capture_render_dev): the model at surfaces [nf,3,3] under leds [Lr,3] -- the
+    fitted lights, some of them, or new positions, 1 <= Lr <= 64 -- as face_values [nf,3,Lr] (the bytes of model_eval on cosines'
+    planes) and as 8-bit BGR images [Lr,H,W,3] in the captures' layout: map pixel (y, x) writes image row H-1-y.  Grey level:
+    t = 255.0 * v + 0.5, clamped to 0 ... 255, NaN -> 0 (render_capture_host is the definition as code).  Pixels that carry no face
+    receive `background`, or with background = -1 keep what `rendered` (a tensor to write into) held."""
+    import torch
+    pixel_map, vertices, faces, face_normals, la, va, surfaces, nf, dev = _render_args(model, pixel_map, vertices, faces, face_normals, leds,
+                                                                                       view_origin, surfaces, validate)
+    H, W, Lr = int(pixel_map.shape[0]), int(pixel_map.shape[1]), int(la.shape[0])
+    values = torch.empty((nf, 3, Lr), dtype=torch.float64, device=dev) if want_values else None
+    if want_images or rendered is not None:
+        rendered = _out_tensor(rendered, (Lr, H, W, 3), torch.uint8, dev, "rendered", torch)
+    _call("brdf_hip_capture_render_dev", dev, int(model), H, W, pixel_map.data_ptr(), vertices.data_ptr(), faces.data_ptr(), face_normals.data_ptr(), nf,
+          _dptr(la), Lr, _dptr(va), int(rv_mode), surfaces.data_ptr(), int(background), None if values is None else values.data_ptr(),
+          None if rendered is None else rendered.data_ptr(), _STREAM)
+    return CaptureRender(values, rendered)
+
+
+class CaptureRenderResiduals(NamedTuple):
+    """What capture_render_residuals returns (CUDA tensors and the host scalar): d = measured - rendered grey level over the compared
+    candidates."""
+    light_count: object       # [Lr,3] int64: the compared candidates per light and channel
+    light_sum: object         # [Lr,3] int64: sum d
+    light_sumsq: object       # [Lr,3] int64: sum d^2
+    face_light_count: object  # [nf,3,Lr] int32
+    face_light_sum: object    # [nf,3,Lr] int64
+    face_light_sumsq: object  # [nf,3,Lr] int64
+    abs_max: object           # [H,W,3] uint8 at map coordinates: max |d| over the pixel's compared lights
+    worst_light: object       # [H,W,3] uint8: the lowest light that attains it; 255 where nothing is compared
+    face_values: object       # [nf,3,Lr] float64
+    n_pixels: int
+
+    def psnr(self):
+        """10 log10(255^2 count / sumsq) in dB: (per light and channel [Lr,3], over all lights and channels).  inf at sumsq = 0, NaN at
+        count = 0."""
+        n, s = self.light_count.cpu().numpy(), self.light_sumsq.cpu().numpy()
+        return _psnr(n, s), float(_psnr(n.sum(), s.sum()))
+
+
+def capture_render_residuals(model: int, images, pixel_map, vertices, faces, face_normals, leds, view_origin, surfaces, *, v_min: int = 0,
+                             v_max: int = 255, cos_min: float = -2.0, rv_mode: int = 0, validate: bool = True,
+                             out: CaptureRenderResiduals | None = None) -> CaptureRenderResiduals:
+    """Where a fit disagrees with images, in grey levels (brdf_hip_capture_render_residuals_dev): images [Lr,H,W,3] taken under leds
+    [Lr,3] -- the fitted lights or held-out ones -- against capture_render's grey levels at surfaces [nf,3,3], without an image being
+    rendered.  The validity rule as fit_capture_masked (the defaults switch it off; a NaN cosine is never a sample).  Every map is
+    integer and written whole; two calls give the same bytes; render_residuals_host is the definition as code.  `out`: an earlier
+    result whose tensors are written into."""
+    import torch
+    args, keep, nf = _capture_args(model, images, pixel_map, vertices, faces, face_normals, leds, view_origin, rv_mode, None, None, None, 0, None,
+                                   validate)
+    dev = keep[0].device
+    Lr, H, W = args[2], args[3], args[4]
+    if not torch.is_tensor(surfaces):
+        surfaces = torch.from_numpy(np.ascontiguousarray(surfaces, dtype=np.float64)).to(dev)
+    surfaces = surfaces.contiguous()
+    _require(surfaces.is_cuda and surfaces.device == dev and surfaces.dtype == torch.float64 and tuple(surfaces.shape) == (nf, 3, 3),
+             "surfaces: [nf,3,3] float64 on the capture's device")
+    o = out if out is not None else CaptureRenderResiduals(*([None] * 9), 0)
+    i64, i32, u8 = torch.int64, torch.int32, torch.uint8
+    maps = (_out_tensor(o.light_count, (Lr, 3), i64, dev, "light_count", torch), _out_tensor(o.light_sum, (Lr, 3), i64, dev, "light_sum", torch),
+            _out_tensor(o.light_sumsq, (Lr, 3), i64, dev, "light_sumsq", torch),
+            _out_tensor(o.face_light_count, (nf, 3, Lr), i32, dev, "face_light_count", torch),
+            _out_tensor(o.face_light_sum, (nf, 3, Lr), i64, dev, "face_light_sum", torch),
+            _out_tensor(o.face_light_sumsq, (nf, 3, Lr), i64, dev, "face_light_sumsq", torch),
+            _out_tensor(o.abs_max, (H, W, 3), u8, dev, "abs_max", torch), _out_tensor(o.worst_light, (H, W, 3), u8, dev, "worst_light", torch, 255),
+            _out_tensor(o.face_values, (nf, 3, Lr), torch.float64, dev, "face_values", torch))
+    npx = C.c_longlong(0)
+    _call("brdf_hip_capture_render_residuals_dev", dev, *args[:13], surfaces.data_ptr(), int(v_min), int(v_max), float(cos_min),
+          *(t.data_ptr() for t in maps), C.byref(npx), _STREAM)
+    return CaptureRenderResiduals(*maps, npx.value)
+
+
+def surfaces_from_materials(face_label, materials, fill=(0.0, 0.0, 0.0), *, out=None):
+    """surfaces [nf,3,3] = materials[face_label] where the label is inside [0, K), `fill` = {kd, ks, n} in each channel elsewhere
+    (brdf_hip_surfaces_from_materials_dev): fit_capture_labelled / fit_capture_materials results -- or, with K = 1 and all labels 0, a
+    single BRDF -- as the surfaces capture_render and capture_render_residuals read.  face_label: CUDA int32 [nf]; materials [K,3,3]
+    CUDA tensor or NumPy."""
+    import torch
+    _require(torch.is_tensor(face_label) and face_label.is_cuda and face_label.dtype == torch.int32 and face_label.dim() == 1 and face_label.is_contiguous(),
+             "face_label: contiguous CUDA int32 [nf]")
+    dev, nf = face_label.device, int(face_label.shape[0])
+    materials = _materials_tensor(materials, dev, torch)
+    surfaces = _out_tensor(out, (nf, 3, 3), torch.float64, dev, "out", torch)
+    _call("brdf_hip_surfaces_from_materials_dev", dev, face_label.data_ptr(), nf, materials.data_ptr(), int(materials.shape[0]), _dptr(_f64(fill, 3)),
+          surfaces.data_ptr(), _STREAM)
+    return surfaces

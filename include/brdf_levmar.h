@@ -815,6 +815,61 @@ int brdf_hip_fit_capture_materials_dev(int model, const unsigned char *d_images,
                                        int *d_count, int *d_label_faces, int *d_face_pixels, int *rounds_used, int *settled, long long *changed,
                                        long long *n_pixels, long long *n_faces, void *stream);
 
+/* ---- rendering a fitted capture --------------------------------------------------------------------------------------------------
+ * Parameters back into images: what the reference program shades the mesh with, as grey levels in the captures' own layout, the
+ * differences to a set of captures, and the surfaces of a labelled result.  All pixels of a face share the face's cosines, so a
+ * prediction depends on (face, channel, light) alone: a value table d_face_values[nf][3][Lr] and integer passes over the pixels.  No fit
+ * or statistics kernel; no float atomics.  Mesh, view_origin, rv_mode, d_pixel_map as brdf_hip_fit_capture_faces_dev; leds[Lr][3] (HOST)
+ * are ANY lights, 1 <= Lr <= 64: the fitted ones, some of them, or new positions; d_brdf_surfaces[nf][3][3] (DEVICE, read only).
+ *
+ * brdf_hip_capture_render_dev -> d_face_values[nf][3][Lr] (DEVICE double, may be NULL), d_rendered[Lr][H][W][3] (DEVICE 8-bit BGR, may
+ * be NULL; not both).
+ *   Value          (f, c, l): the model at d_brdf_surfaces[f][c] on face f's cosine triple under light l, on the exact path: the BYTES
+ *                  of brdf_hip_model_eval_dev on brdf_hip_cosines_dev's planes for these lights.  Written for EVERY face.
+ *   Grey level     t = 255.0 * v + 0.5;  q = !(t >= 0) ? 0 : (t >= 256.0 ? 255 : (int)t): a NaN value gives 0.
+ *   Image          map pixel (y, x) with a face in [0, nf) writes q of (face, c, l) to d_rendered[l][H-1-y][x][c], the place the captures
+ *                  read; any other pixel receives `background` (0 ... 255), or with background = -1 is left untouched.
+ *   Cost           Lr H W 3 bytes written once, in 16-byte stores between the ends of each image; 8 + 1 bytes per (face, channel, light)
+ *                  of tables.
+ *   Refused before any HIP call, under the entry's name: a NULL required pointer (map, mesh, leds, view origin, brdf_surfaces), both
+ *                  outputs NULL, Lr outside [1, 64], H, W or nf <= 0, 3 nf > INT_MAX, an unknown model, rv_mode not 0 or 1, background
+ *                  outside [-1, 255].
+ *
+ * brdf_hip_capture_render_residuals_dev: the captures d_images[Lr][H][W][3] under these lights against the rendered grey levels, without
+ * an image being rendered.  The validity rule v_min, v_max, cos_min as brdf_hip_fit_capture_masked_dev's (0, 255, cos_min < -1: off; a NaN
+ * cosine is never a sample).
+ *   Candidates     (carried pixel, light l, channel c); COMPARED iff it passes the rule.  d = measured - q, an integer in -255 ... 255.
+ *   Outputs        DEVICE, each may be NULL.  d_light_count / _sum / _sumsq[Lr][3] (long long): the compared candidates, sum d, sum d^2;
+ *                  d_face_light_count[nf][3][Lr] (int), d_face_light_sum / _sumsq[nf][3][Lr] (long long): the same per face, written
+ *                  for EVERY face (zeros where no pixel carries it); d_abs_max[H][W][3], d_worst_light[H][W][3] (8-bit, at MAP
+ *                  coordinates): max |d| over the pixel's compared lights and the light that attains it, the lowest on a tie -- 0 and
+ *                  255 where nothing is compared and on background pixels; d_face_values as above; n_pixels (HOST): the carried pixels.
+ *   Determinism    integer adds (LDS integer atomics, then one global integer atomic per touched word): their order cannot show, two
+ *                  calls give the same bytes.
+ *   Memory         24 bytes per carried pixel and the sort's scratch for the grouping, 9 bytes per (face, channel, light).
+ *   Refused before any HIP call, under the entry's name: a NULL required pointer (images, map, mesh, leds, view origin, brdf_surfaces),
+ *                  Lr outside [1, 64], H, W or nf <= 0, 3 nf > INT_MAX, an unknown model, rv_mode not 0 or 1, v_min > v_max, a NaN
+ *                  cos_min.
+ *
+ * brdf_hip_surfaces_from_materials_dev: d_brdf_surfaces[f] = d_materials[d_face_label[f]] where the label is in [0, K), elsewhere
+ * fill[3] (HOST: {kd, ks, n}) in each channel.  K = 1 with all labels 0 is the single-BRDF case: with it brdf_hip_fit_capture_labelled_dev,
+ * _materials_dev and _single_faces_dev results render through the two entries above.  Refused before any HIP call: a NULL pointer,
+ * nf <= 0, 3 nf > INT_MAX, K < 1.
+ * All three synchronise `stream` before returning and return 0, or LM_ERROR for bad arguments or a HIP failure with a message that
+ * names the entry in brdf_hip_last_error().  Not covered: float or HDR output, a tone curve, shadows or visibility, per-vertex shading. */
+int brdf_hip_capture_render_dev(int model, int H, int W, const int *d_pixel_map, const double *d_vertices, const int *d_faces,
+                                const double *d_face_normals, int nf, const double *leds, int Lr, const double *view_origin, int rv_mode,
+                                const double *d_brdf_surfaces, int background, double *d_face_values, unsigned char *d_rendered, void *stream);
+int brdf_hip_capture_render_residuals_dev(int model, const unsigned char *d_images, int Lr, int H, int W, const int *d_pixel_map,
+                                          const double *d_vertices, const int *d_faces, const double *d_face_normals, int nf, const double *leds,
+                                          const double *view_origin, int rv_mode, const double *d_brdf_surfaces, int v_min, int v_max,
+                                          double cos_min, long long *d_light_count, long long *d_light_sum, long long *d_light_sumsq,
+                                          int *d_face_light_count, long long *d_face_light_sum, long long *d_face_light_sumsq,
+                                          unsigned char *d_abs_max, unsigned char *d_worst_light, double *d_face_values, long long *n_pixels,
+                                          void *stream);
+int brdf_hip_surfaces_from_materials_dev(const int *d_face_label, int nf, const double *d_materials, int K, const double *fill,
+                                         double *d_brdf_surfaces, void *stream);
+
 /* ---- diagnostics ----------------------------------------------------------------------------------- */
 int brdf_hip_device_count(void);
 const char *brdf_hip_last_error(void);
