@@ -7,7 +7,6 @@
 
 namespace brdf {
 
-constexpr int kMaterialGroup = 4;     // materials a residual chunk evaluates per read of its samples
 constexpr int kMaterialRoundsMax = 64;  // brdf_hip_fit_capture_materials_dev: rounds in [0, kMaterialRoundsMax]
 
 int capture_face_residuals_run(const CaptureResidualsArgs &a);  // refuses bad arguments before any HIP call

@@ -19,7 +19,7 @@ from tests import test_gpu_capture_single_faces as S
 
 pytestmark = pytest.mark.gpu
 SENTINEL = S.SENTINEL
-GROUP = 4  # capture_materials.h: kMaterialGroup
+GROUP = 4  # capture_face_major.h: kMaterialGroup
 
 
 @pytest.fixture(scope="module")
