@@ -18,3 +18,6 @@ from .fit import (METHOD_BC_DER, METHOD_BC_DIF, METHOD_DER, METHOD_DIF, MODEL_BL
                   group_capture_label_samples, assign_materials, seed_materials,
                   CaptureRender, CaptureRenderResiduals, RenderResidualsHost, capture_render, capture_render_residuals, surfaces_from_materials,
                   render_capture_host, render_residuals_host)
+from . import raster  # noqa: F401
+from .raster import (PixelMap, face_normals, face_normals_host, pixel_map, pixel_map_host, project_host, gl_frustum, gl_look_at, make_frustum,  # noqa: F401
+                     parse_cal, tsai_camera)

@@ -93,6 +93,9 @@ ABI = {
     "brdf_hip_cosines_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, D, C.c_int, D, C.c_int,
                                        C.c_void_p, C.c_void_p]),
     "brdf_hip_led_table": (None, [D]),
+    "brdf_hip_face_normals_dev": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "brdf_hip_pixel_map_dev": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, D, D, D, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
     "brdf_hip_fit_capture_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, C.c_void_p, D,
                                            C.POINTER(C.c_longlong), C.c_void_p]),

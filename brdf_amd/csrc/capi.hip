@@ -22,6 +22,7 @@
 #include "fit_stats.h"
 #include "clip_fit.h"
 #include "packed_fit.h"
+#include "pixel_map.h"
 #include "weighted_fit.h"
 
 using namespace brdf;
@@ -778,6 +779,18 @@ int brdf_hip_cosines_dev(const double *d_vertices, const int *d_faces, const dou
 }
 
 void brdf_hip_led_table(double *leds16x3) { led_table(leds16x3); }
+
+int brdf_hip_face_normals_dev(const double *d_vertices, long long nv, const int *d_faces, long long nf, double *d_normals, void *stream) {
+  return face_normals_run(d_vertices, nv, d_faces, nf, d_normals, static_cast<hipStream_t>(stream));
+}
+
+int brdf_hip_pixel_map_dev(const double *d_vertices, long long nv, const int *d_faces, long long nf, const double *model_view,
+                           const double *projection, const double *viewport, int H, int W, int mode, int cull, int *d_pixel_map,
+                           double *d_depth, int *d_face_pixels, long long *stats, void *stream) {
+  const PixelMapArgs a = {d_vertices, nv, d_faces, nf, model_view, projection, viewport, H, W, mode, cull, d_pixel_map, d_depth, d_face_pixels,
+                          stats, static_cast<hipStream_t>(stream)};
+  return pixel_map_run(a);
+}
 
 // the capture entries (capture_fit.h): what all seven take, in the order of CaptureArgs
 #define CAPTURE_ARGS \

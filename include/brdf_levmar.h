@@ -446,6 +446,49 @@ int brdf_hip_model_eval_dev(int model, const double *d_angles, int n, const doub
 int brdf_hip_synth_dev(int model, unsigned long long seed, long long first, int count, int n,
                        const double *d_truth, double *d_angles, double *d_x, void *stream);
 
+/* ---- mesh + camera -> the capture entries' inputs: face normals and the pixel-to-face map ------------------ */
+/* CBRDFdata::CalcFaceNormals (brdfdata.cpp:314-330) on the device, one lane per face:
+ *   e1 = v2 - v1, e2 = v3 - v1, n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), then Eigen's normalize():
+ *   if ((n0^2 + n1^2) + n2^2 > 0) every component is divided by its square root, otherwise n stays as it is.
+ * d_vertices[nv][3], d_faces[nf][3], d_normals[nf][3]: device.  A face with a vertex index outside [0, nv) gets a NaN normal.
+ * Enqueues on `stream` and returns: 0, or LM_ERROR with a message in brdf_hip_last_error() (a null pointer; nv or nf outside
+ * 1 ... INT_MAX: refused before any HIP call). */
+int brdf_hip_face_normals_dev(const double *d_vertices, long long nv, const int *d_faces, long long nf, double *d_normals,
+                              void *stream);
+
+/* The pixel map every capture entry reads, from the mesh and the camera: replaces CBRDFdata::CalcPixel2SurfaceMapping
+ * (brdfdata.cpp:629-681), which needs a live GL context.  model_view[16], projection[16] (column-major, as glGetDoublev returns
+ * them) and viewport[4] are HOST arrays: the application's three glGet* results go in unchanged.
+ *   Projection     gluProject's arithmetic: out_i = ((in0 m[i] + in1 m[4+i]) + in2 m[8+i]) + in3 m[12+i] with model_view (in3 = 1),
+ *                  then with projection; w == 0 or anything not finite: the vertex is unprojectable; otherwise x, y, z are divided
+ *                  by w, t = v 0.5 + 0.5, winX = t_x viewport[2] + viewport[0], winY likewise, winZ = t_z.
+ *   mode 0         the reference's map: per face the centroid ((a + b) + c) / 3.0 per coordinate, projected;
+ *                  if (winY >= 0 && winX >= 0) map[(int)winY][(int)winX] = face.  Of several faces in one pixel the HIGHEST index
+ *                  wins (the reference's serial loop lets the last one win).  One deviation: the reference never checks the upper
+ *                  bound and writes out of bounds; here (int)winX >= W or (int)winY >= H writes nothing and is counted.
+ *   mode 1         rasterised and z-buffered.  A face is dropped when a vertex is unprojectable or has w <= 0 after the projection
+ *                  matrix (there is no near-plane clipping), when its window-space area
+ *                  A = (bx - ax)(cy - ay) - (by - ay)(cx - ax) is 0 or not finite, or when cull = 1 and A < 0.  Pixel (col, row) is
+ *                  covered iff the three edge functions at its centre p = (col + 0.5, row + 0.5),
+ *                    E0 = (bx - px)(cy - py) - (by - py)(cx - px), E1 = (cx - px)(ay - py) - (cy - py)(ax - px),
+ *                    E2 = (ax - px)(by - py) - (ay - py)(bx - px),
+ *                  each multiplied by the sign of A, are all >= 0 (inclusive: two faces sharing an edge both cover a centre on it)
+ *                  and its depth z = ((E0 az + E1 bz) + E2 cz) / A lies in [0, 1].  The pixel's owner is the covering face of
+ *                  least z, and among equal z the lowest face index.  Candidates are the pixels whose centres lie in the face's
+ *                  bounding box, clamped to the viewport [0, W) x [0, H).
+ *   d_pixel_map[H][W]  int32: face index or -1; row y is window row y, bottom-up -- the layout every capture entry reads.
+ *   d_depth[H][W]      double, or NULL: the owner's z (mode 0: the centroid's winZ); 2.0 where no face owns the pixel.
+ *   d_face_pixels[nf]  int32, or NULL: the number of pixels each face owns.
+ *   stats[8]           HOST, or NULL: faces rasterised (mode 0: centroids written); faces dropped as unprojectable or w <= 0 (or
+ *                      with a vertex index outside [0, nv)); dropped as degenerate; culled; wholly outside the viewport (mode 0:
+ *                      winX < 0 or winY < 0); candidates visited; pixels owned; writes refused by mode 0's upper bound.
+ * The result is exact and deterministic (integer atomics only): two calls give the same bytes.  Refused before any HIP call: H, W < 1,
+ * H W, nv or nf beyond INT_MAX, nv or nf < 1, mode or cull outside 0 | 1, a null required pointer, a matrix or viewport entry that
+ * is not finite, viewport[2] or viewport[3] <= 0.  Synchronises `stream` before returning.  Returns 0 or LM_ERROR. */
+int brdf_hip_pixel_map_dev(const double *d_vertices, long long nv, const int *d_faces, long long nf, const double *model_view,
+                           const double *projection, const double *viewport, int H, int W, int mode, int cull, int *d_pixel_map,
+                           double *d_depth, int *d_face_pixels, long long *stats, void *stream);
+
 /* ---- the step before the fit: vectors -> cosines ---------------------------- */
 /* Replaces CBRDFdata::GetCosLN / GetCosNH / GetCosRV (brdfdata.cpp:859-899, :902-943, :799-857), which the reference
  * evaluates per pixel / per face and per light on the host.  One launch fills, for S surfels, the three cosine planes
