@@ -21,3 +21,6 @@ from .fit import (METHOD_BC_DER, METHOD_BC_DIF, METHOD_DER, METHOD_DIF, MODEL_BL
 from . import raster  # noqa: F401
 from .raster import (PixelMap, face_normals, face_normals_host, pixel_map, pixel_map_host, project_host, gl_frustum, gl_look_at, make_frustum,  # noqa: F401
                      parse_cal, tsai_camera)
+from . import shadow  # noqa: F401
+from .shadow import (AppliedVisibility, LightVisibility, apply_visibility, apply_visibility_host, light_visibility, light_visibility_host,  # noqa: F401
+                     lit_matrix)

@@ -96,6 +96,10 @@ ABI = {
     "brdf_hip_face_normals_dev": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     "brdf_hip_pixel_map_dev": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, D, D, D, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
+    "brdf_hip_light_visibility_dev": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, D, C.c_int, C.c_double, C.c_void_p,
+                                                C.POINTER(C.c_longlong), C.c_void_p]),
+    "brdf_hip_capture_apply_visibility_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p]),
     "brdf_hip_fit_capture_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_int, D, D, C.c_int, D, D, D, C.c_int, D, C.c_void_p, D,
                                            C.POINTER(C.c_longlong), C.c_void_p]),

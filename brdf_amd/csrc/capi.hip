@@ -21,6 +21,7 @@
 #include "fit_host.h"
 #include "fit_stats.h"
 #include "clip_fit.h"
+#include "light_visibility.h"
 #include "packed_fit.h"
 #include "pixel_map.h"
 #include "weighted_fit.h"
@@ -790,6 +791,19 @@ int brdf_hip_pixel_map_dev(const double *d_vertices, long long nv, const int *d_
   const PixelMapArgs a = {d_vertices, nv, d_faces, nf, model_view, projection, viewport, H, W, mode, cull, d_pixel_map, d_depth, d_face_pixels,
                           stats, static_cast<hipStream_t>(stream)};
   return pixel_map_run(a);
+}
+
+int brdf_hip_light_visibility_dev(const double *d_vertices, long long nv, const int *d_faces, long long nf, const double *d_normals,
+                                  const double *leds, int L, double t_min, unsigned long long *d_face_lit, long long *stats, void *stream) {
+  const LightVisibilityArgs a = {d_vertices, nv, d_faces, nf, d_normals, leds, L, t_min, d_face_lit, stats, static_cast<hipStream_t>(stream)};
+  return light_visibility_run(a);
+}
+
+int brdf_hip_capture_apply_visibility_dev(const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                          const unsigned long long *d_face_lit, int nf, int level, unsigned char *d_out,
+                                          unsigned long long *d_shadowed, void *stream) {
+  const ApplyVisibilityArgs a = {d_images, L, H, W, d_pixel_map, d_face_lit, nf, level, d_out, d_shadowed, static_cast<hipStream_t>(stream)};
+  return apply_visibility_run(a);
 }
 
 // the capture entries (capture_fit.h): what all seven take, in the order of CaptureArgs

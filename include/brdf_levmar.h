@@ -489,6 +489,49 @@ int brdf_hip_pixel_map_dev(const double *d_vertices, long long nv, const int *d_
                            const double *projection, const double *viewport, int H, int W, int mode, int cull, int *d_pixel_map,
                            double *d_depth, int *d_face_pixels, long long *stats, void *stream);
 
+/* ---- cast shadows: which lights a face can see, and that visibility painted into the captures ---------------- */
+/* Per face one 64-bit word, bit l set iff light l is visible from the face's centre.  The reference has no counterpart (its
+ * voxel-grid shadow code in brdfdata.cpp is commented out).  d_vertices[nv][3], d_faces[nf][3], d_normals[nf][3] (or NULL) and
+ * d_face_lit[nf] are device arrays; leds[L][3], 1 <= L <= 64, and stats[5] (or NULL) are HOST arrays.
+ *   dot3(x, y) = (x0 y0 + x1 y1) + x2 y2;   x cross y = (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0).
+ *   Valid face     its three indices lie in [0, nv) and its nine coordinates are finite.  An invalid face has lit = 0 and
+ *                  occludes nothing.
+ *   Origin         o[k] = ((a[k] + b[k]) + c[k]) / 3.0 of the face's corners a, b, c: the centre the cosines use.
+ *   Direction      d = P_l - o.
+ *   Facing away    with normals: !(dot3(n_f, d) > 0).  The bit is clear; the pair counts in stats[2] and in neither stats[3] nor
+ *                  stats[4].  Without normals no pair faces away.
+ *   Shadowed       otherwise, iff some valid face g != f is hit; with v0, v1, v2 the corners of g:
+ *                    e1 = v1 - v0, e2 = v2 - v0, h = d cross e2, a = dot3(e1, h), s = o - v0, q = s cross e1,
+ *                    U = dot3(s, h), V = dot3(d, q), T = dot3(e2, q); if a < 0, U, V and T are negated; A = |a|;
+ *                    hit iff A > 0 && U >= 0 && V >= 0 && U + V <= A && T > t_min A && T < (1.0 - t_min) A.
+ *                  No division.  Edges are inclusive; a ray parallel to the occluder's plane misses; a NaN misses; an occluder
+ *                  beyond the light or behind the origin casts nothing.  Coplanar neighbours do not shadow each other: the
+ *                  origin is interior to f, and T is rounding noise below t_min A.
+ *   Lit            a pair that neither faces away nor is shadowed.
+ *   stats[5]       valid faces, invalid faces, pairs (valid face, light) facing away, pairs lit, pairs shadowed.
+ * Brute force, nf^2 L tests and no acceleration structure: the result depends on mesh and rig alone, so it is computed once per
+ * capture session.  Exact and deterministic (integer atomicAnd on the words only): two calls give the same bytes, those of the
+ * NumPy twin brdf_amd.light_visibility_host.  Workspace O(nf).  Refused before any HIP call: a null required pointer, L outside
+ * [1, 64], nv or nf < 1 or beyond INT_MAX, a light coordinate that is not finite, t_min outside [0, 0.5) or a NaN.  Synchronises
+ * `stream` before returning.  Returns 0 or LM_ERROR. */
+int brdf_hip_light_visibility_dev(const double *d_vertices, long long nv, const int *d_faces, long long nf, const double *d_normals,
+                                  const double *leds, int L, double t_min, unsigned long long *d_face_lit, long long *stats,
+                                  void *stream);
+
+/* The visibility words into images: for light l and map pixel (y, x) whose entry f lies in [0, nf) and whose bit l of
+ * d_face_lit[f] is clear, the three bytes at image row H - 1 - y, column x of image l become `level` (0 ... 255) -- the captures'
+ * layout, as brdf_hip_capture_render_dev writes it.  Every other byte of d_out[L][H][W][3] is d_images'.  d_out may be d_images
+ * itself (in place: only painted bytes are written); a buffer that overlaps it in part is refused.  d_shadowed[L] (device, or
+ * NULL): the painted pixels per light.  Bit l means image l: for held-out lights compute a word for those lights.
+ * This carries shadows into EVERY capture entry without a change to any of them: paint level = 0 and fit with v_min >= 1.  A mask
+ * argument in the grouped validity rule itself, which would also serve v_min = 0 callers, would change every capture entry's ABI
+ * and is left out on purpose.  One pass over the images.  Refused before any HIP call: a null required pointer, L outside
+ * [1, 64], H, W or nf < 1, H W beyond INT_MAX, level outside 0 ... 255, a partial overlap.  Enqueues on `stream` and returns 0 or
+ * LM_ERROR. */
+int brdf_hip_capture_apply_visibility_dev(const unsigned char *d_images, int L, int H, int W, const int *d_pixel_map,
+                                          const unsigned long long *d_face_lit, int nf, int level, unsigned char *d_out,
+                                          unsigned long long *d_shadowed, void *stream);
+
 /* ---- the step before the fit: vectors -> cosines ---------------------------- */
 /* Replaces CBRDFdata::GetCosLN / GetCosNH / GetCosRV (brdfdata.cpp:859-899, :902-943, :799-857), which the reference
  * evaluates per pixel / per face and per light on the host.  One launch fills, for S surfels, the three cosine planes
